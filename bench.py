@@ -274,6 +274,42 @@ def k11_probe(cfg, B, world, dev, n=25):
     return out
 
 
+def dump_outputs(out_dir, returned, ps, budget_bytes=60 << 20):
+    """--dump-outputs: what the last timed step handed its caller (the model output's tensors; the engine's step dict with --api engine,
+    without its host-side splice plan) plus the trainable set's flat fp32 gradient and its fp32 master weights after the optimizer step,
+    one DIR/<name>.npy each in float32 (float64 for float64 / integer tensors).  Fields the step left lazy (logits a caller has not read) were
+    not computed by it and are not written.  An array larger than its share of the budget is a fixed, seeded sample of its flattened values
+    (the same indices in every run), so two builds can be compared array for array."""
+    import numpy as np
+    found = []
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            found.append((name, v))
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                if not (name == "" and k == "plan"):
+                    walk(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}", x)
+    walk("", returned if isinstance(returned, dict) else dict(vars(returned)))     # vars(): lazy fields stay unread
+    found += [("trainable_grad", ps.grad), ("trainable_master", ps.master)]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in found:
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        cap = min(1 << 20, budget_bytes // len(found) // (8 if dt == torch.float64 else 4))
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, "".join(c if c.isalnum() or c in "._-" else "_" for c in name) + ".npy"), a)
+        total += a.nbytes
+    sys.stderr.write(f"bench.py: wrote {len(found)} arrays ({total / 2 ** 20:.1f} MiB) of the last timed step to {out_dir}\n")
+
+
 def _checksum(t):
     """(sum, sum of |x|, xor of the raw bits) of a device tensor as python numbers: equal on every rank iff the tensors are bit-identical
     (up to xor / sum collisions).  Bench-side diagnosis only."""
@@ -415,6 +451,8 @@ def launch_ranks(args):
     env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or n) // n)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:                                   # the ranks run in ROOT: hand them the directory the caller meant (last flag wins)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     limit = float(os.environ.get("VP_BENCH_LAUNCH_TIMEOUT", "2400"))
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, start_new_session=True, cwd=ROOT)
     try:
@@ -478,7 +516,12 @@ def main():
                          "region and one behind the fence that closes it, so tools/kernel_stats_steps.py can cut the kernel trace to the timed steps")
     ap.add_argument("--same-batch", action="store_true", help="A/B aid: replay one batch (splice-plan cache hit) instead of a fresh one per step")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even with one rank (test hook)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its returned tensors, the trainable gradient and the "
+                         "updated fp32 weights) as DIR/<name>.npy, 64 MB at most (large arrays: a fixed, seeded sample); rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)                              # never returns
@@ -591,6 +634,7 @@ def main():
     total_steps = 2181                                  # LLaVA-558K / global batch 256 (scripts/train/pretrain.sh), 3 % warm-up, cosine
     n_warm = optim.warmup_steps(total_steps, 0.03)
     it = [0]
+    returned = [None]                                   # --dump-outputs: what the last step handed its caller
 
     def step():
         b = fresh[it[0] % n_total] if not args.same_batch else fresh[0]
@@ -598,6 +642,7 @@ def main():
         if model is None:
             out = eng.train_step(b)
             eng.optimizer_step(lr=args.lr, lr_mult=lr_mult)                  # wd 0, no clipping: pretrain.sh
+            res = out
         else:
             # what the reference's trainer does per micro-batch (HF Trainer.training_step under ola_vlm_train.py:1297-1327): forward through
             # the model class, backward through autograd, optimizer, zero_grad
@@ -611,6 +656,8 @@ def main():
             model.zero_grad(set_to_none=True)
             out = model._last
             out["loss"] = res.loss.detach()
+        if args.dump_outputs:
+            returned[0] = res
         it[0] += 1
         return out
 
@@ -658,6 +705,9 @@ def main():
         return float(t)
 
     dt_own, out, prof = timed_leg(args.warmup, args.steps, profile=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, returned[0], eng.ps)         # before any later step (probes, other legs) reuses the buffers
+    returned[0] = None
     dt = max_over_ranks(dt_own)
     diag = None
     if dist is not None:

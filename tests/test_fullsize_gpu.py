@@ -218,7 +218,7 @@ def test_overlapped_steps_equal_synchronised_steps_full_width(stage):
     assert torch.equal(a, b_), (a, b_)
 
 
-def test_attention_d128_generic_forward_matches_default():
+def test_attention_d128_generic_forward_matches_default(tmp_path):
     """The generic 16-row forward (VP_ATTN_FWDM=0) against the default 32x32x16 swapped-product kernel on the decoder shape: same lse and
     outputs up to bf16 rounding (different max bookkeeping), incl. ragged kv_len and a sliding window."""
     import os
@@ -242,7 +242,7 @@ torch.save(outs, os.environ["VP_OUT"])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     for flag in ("0", "1"):
-        out = f"/tmp/vp_attn_ab_{flag}.pt"
+        out = str(tmp_path / f"vp_attn_ab_{flag}.pt")
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, VP_ROOT=root, VP_OUT=out, VP_ATTN_FWDM=flag),
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
