@@ -203,6 +203,44 @@ int vp_attn_bwd_rope(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void*
                      void* dv, long dv_bs, long dv_ts, float* delta, const int* kv_len, int causal, int window, float scale,
                      const float* rope_cos, const float* rope_sin, const int* rope_pos, vp_stream_t stream);
 
+/* ---- single-token decode (KV-cached generation).  The reference scores every checkpoint by generating text: HF's generation loop over
+ * `inputs_embeds` after the multimodal splice (base_ola_vlm.py:579-616, llava_llama.py:122), called from eval/model_cvbench_loader.py:127,
+ * eval/model_mmstar_loader.py:125 and demo.py:328 with use_cache=True.  One token per sequence: every decoder GEMM has M = B <= 16 rows and
+ * is bound by its weight's bytes.
+ * vp_decode_gemm: C[M,N] = epi(norm(A)[M,K] . W[N,K]^T) for 1 <= M <= 16 (HF LlamaAttention q/k/v/o_proj, LlamaMLP gate/up/down_proj and
+ *   lm_head at one position).  W is read once, straight into registers.  norm_w non-NULL: RMSNorm prologue (HF LlamaRMSNorm: every block
+ *   computes rstd of the A rows over K itself and applies gamma = norm_w [K] while loading A; vp_rmsnorm_fwd's rounding points).
+ *   epilogue VP_EPI_NONE: bf16 out, or fp32 out (out_f32 = 1: the lm_head logits, ola_llama.py:121-122 `.float()`); residual non-NULL:
+ *   C = bf16(bf16(acc) + residual) (o_proj / down_proj residual adds); VP_EPI_SWIGLU_IL / VP_EPI_SWIGLU_HALVES: W is the fused gate|up
+ *   weight (interleaved 8-row chunks as ops.interleave_gate_up lays it out / [gate | up] halves), C = silu(gate) * up [M, N/2].  Shapes whose
+ *   N has too few 16-row tiles to fill the chip also split K over blocks: `workspace` = vp_decode_gemm_workspace_bytes(M, N, K, epilogue)
+ *   bytes of caller-owned device memory (0 = none needed; NULL then allowed), summed in a fixed order (bit-identical run to run).
+ *   K, lda, ldw multiples of 8, A / W / norm_w 16-byte aligned. */
+#define VP_EPI_SWIGLU_IL 4
+#define VP_EPI_SWIGLU_HALVES 5
+long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual, long ldr,
+                   const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, vp_stream_t stream);
+/* RoPE of the new token and the KV append (HF apply_rotary_pos_emb + DynamicCache.update, modeling_llama.py, at position pos[b] of each
+ * sequence): qkv [B, ldqkv] rows (Hq q heads | Hkv k heads | Hkv v heads, head_dim D); q rotated into q_out [B, ldq]; k rotated and v copied
+ * into row pos[b] of the caches ([B, Smax, Hkv, D] views, strides in elements).  cos_t / sin_t: fp32 [>= Smax, D/2] (ops.rope_tables); pos:
+ * int32 [B] on the device (a captured step stays valid from token to token); rows with pos[b] outside [0, Smax) are not written.  Rounding
+ * points of vp_rope. */
+int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
+                          long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t, const int* pos, int Smax,
+                          vp_stream_t stream);
+/* Decode attention (HF LlamaAttention / Phi3Attention eager path at one query row: fp32 softmax over the cached keys): q [B, Hq*D] rows
+ * (stride q_bs), K / V caches [B, Smax, Hkv, D] (strides in elements), kv_len: int32 [B] on the device (keys 0 .. kv_len-1; with window > 0
+ * only keys with kv_len - 1 - key < window, Engine._attn_window's convention), o [B, Hq*D] bf16 (stride o_bs).  The Hq/Hkv query heads of a
+ * KV head share every K / V read; the key range is split over `nsplit` blocks (Smax <= 512 * nsplit), combined in a fixed order.  workspace:
+ * vp_decode_attn_workspace_bytes(B, Hq, Hkv, D, nsplit) bytes, caller-owned.  D in {32, 64, 96, 128}, Hq/Hkv in {1, 2, 4, 8}. */
+long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit);
+int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts, const void* v,
+                   long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
+                   vp_stream_t stream);
+/* x[i] += delta for n int32 on the device (the per-sequence position / length counters of a decode step, advanced without a host round trip) */
+int vp_add_i32(long n, int* x, int delta, vp_stream_t stream);
+
 /* ---- losses.  NTP CE (ola_llama.py:121-136: logits.float(), shifted CrossEntropyLoss, ignore -100);
  * embedding distillation (base_ola_vlm.py:289-320 _emb_loss; ola_utils.py:108-125
  * calculate_contrastive_loss; :96-106 dist_collect -> tgt_all is the rank-ordered all-gather). */

@@ -1,0 +1,114 @@
+"""KV-cached generation timing at full model size (random init, params.init_value): prefill of one image + ~1.5k text tokens, then ms per
+generated token for B = 1 and B = 8 over --new tokens, with and without the captured step, and the host's enqueue time per step.  Prints
+one JSON line (and writes it to --out).  Kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script
+(--profile: fewer tokens, B = 1 and 8, graph on).
+
+  python tools/decode_bench.py --model llama3 --out profiles/decode_bench_llama3.json
+  python tools/decode_bench.py --model phi3 --out profiles/decode_bench_phi3.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def build(model, layers):
+    from visper_lm_amd.config import llama3_8b, phi3_mini
+    from visper_lm_amd.engine import Engine
+    kw = dict(aux_mode="", num_task_tokens=0)
+    if layers:
+        kw["num_hidden_layers"] = layers
+    cfg = llama3_8b(**kw) if model == "llama3" else phi3_mini(**kw)
+    eng = Engine(cfg)
+    eng.init_random(seed=0)
+    return eng
+
+
+def prompt(eng, B, text_tokens, seed=0):
+    from visper_lm_amd.config import IMAGE_TOKEN_INDEX
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(1, 30000, (B, text_tokens), generator=g)
+    ids[:, 5] = IMAGE_TOKEN_INDEX
+    cfg = eng.cfg
+    side = cfg.cnx_image if cfg.is_convnext else cfg.vit_image
+    images = torch.randn(B, 3, side, side, generator=g).to(torch.bfloat16).cuda()
+    return ids, images
+
+
+def time_decode(eng, B, new, text_tokens, use_graph):
+    from visper_lm_amd import decode
+    ids, images = prompt(eng, B, text_tokens)
+    sess = decode.DecodeSession(eng)
+    sess.use_graph = use_graph
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    logits = sess.prefill(ids, None, images, None, new + 1)
+    torch.cuda.synchronize()
+    prefill_ms = (time.perf_counter() - t0) * 1e3
+    tok = torch.argmax(logits, -1)
+    logits = sess.step(tok)                                   # first step: capture (graph) / warm-up (eager), not timed
+    tok = torch.argmax(logits, -1)
+    torch.cuda.synchronize()
+    enq = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(new - 1):
+        h0 = time.perf_counter()
+        logits = sess.step(tok)
+        enq.append((time.perf_counter() - h0) * 1e3)
+        tok = torch.argmax(logits, -1)                       # on the device: no host round trip inside the timed loop
+    e1.record()
+    torch.cuda.synchronize()
+    per_tok = e0.elapsed_time(e1) / (new - 1)
+    enq.sort()
+    return dict(B=B, prompt_rows=int(sess.cache.lens_host.max()) - new, prefill_ms=round(prefill_ms, 2), ms_per_token=round(per_tok, 4),
+                host_enqueue_ms_per_token_median=round(enq[len(enq) // 2], 4), graph=use_graph, tokens_timed=new - 1)
+
+
+def weight_bytes(eng):
+    cfg = eng.cfg
+    H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+    nqkv = (cfg.num_attention_heads + 2 * cfg.num_key_value_heads) * cfg.head_dim
+    dec = L * 2 * (nqkv * H + H * cfg.num_attention_heads * cfg.head_dim + 2 * I * H + H * I)
+    return dec, 2 * cfg.vocab_size * H
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="llama3", choices=["llama3", "phi3"])
+    ap.add_argument("--layers", type=int, default=0, help="0 = the full depth")
+    ap.add_argument("--text", type=int, default=1500)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--profile", action="store_true", help="graph on only (for a rocprofv3 --kernel-trace --stats run)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "decode_bench needs a GPU"
+    eng = build(a.model, a.layers)
+    dec_b, head_b = weight_bytes(eng)
+    res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
+               roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
+    for B in [int(x) for x in a.batches.split(",")]:
+        for g in ((True,) if a.profile else (True, False)):
+            r = time_decode(eng, B, a.new, a.text, g)
+            kv_bytes_per_pos = 2 * 2 * eng.cfg.num_key_value_heads * eng.cfg.head_dim * eng.cfg.num_hidden_layers
+            r["kv_gb_mid_decode"] = round(B * (r["prompt_rows"] + a.new // 2) * kv_bytes_per_pos / 1e9, 3)
+            r["weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 8e12 * 1e3 / r["ms_per_token"], 3)
+            res["runs"].append(r)
+            print(json.dumps(r), flush=True)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

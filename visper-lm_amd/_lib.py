@@ -66,6 +66,13 @@ _SIGS = {
                     i, i, f, p],
     "vp_attn_bwd_rope": [i, i, i, i, i, i, p, l, l, p, l, l, p, l, l, p, l, l, p, p, l, l, p, l, l, p, l, l, p, l, l, p, p,
                     i, i, f, p, p, p, p],
+    # single-token decode (KV-cached generate(): base_ola_vlm.py:579-616, llava_llama.py:122)
+    "vp_decode_gemm_workspace_bytes": [i, i, i, i],
+    "vp_decode_gemm": [i, i, i, p, l, p, l, p, l, p, l, p, f, i, i, p, p],
+    "vp_decode_rope_append": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, p, p, i, p],
+    "vp_decode_attn_workspace_bytes": [i, i, i, i, i],
+    "vp_decode_attn": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, p, i, f, i, p, p],
+    "vp_add_i32": [l, p, i, p],
     "vp_ce_fwd_bwd": [l, i, p, l, p, p, f, i, p],
     "vp_emb_loss_workspace": [i, i, l],
     "vp_sumsq_nblk": [l],
@@ -84,7 +91,8 @@ _SIGS = {
     "vp_comm_info": [p, p, p],
     "vp_comm_destroy": [p],
 }
-_RET_LONG = {"vp_emb_loss_workspace", "vp_gemm_sched_workspace_bytes", "vp_emb_loss_counter_bytes"}
+_RET_LONG = {"vp_emb_loss_workspace", "vp_gemm_sched_workspace_bytes", "vp_emb_loss_counter_bytes", "vp_decode_gemm_workspace_bytes",
+             "vp_decode_attn_workspace_bytes"}
 EXPORTS = ["vp_last_error_string"] + list(_SIGS)
 # measurement / development entry points (include/visper_hip_debug.h): present only in a -DVP_DEBUG build; bound when the library has them
 _DEBUG_SIGS = {

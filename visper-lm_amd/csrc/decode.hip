@@ -1,0 +1,452 @@
+// Single-token decode kernels (KV-cached generation): the reference generates with HF's generation loop over `inputs_embeds`
+// (base_ola_vlm.py:579-616, llava_llama.py:122; called by eval/model_cvbench_loader.py:127, model_mmstar_loader.py:125, demo.py:328).
+// At one token per sequence every decoder GEMM has M = B <= 16 rows and is bound by the bytes of its weight, not by MFMA work:
+//  - decode_gemm_kernel: C[M,N] = epi(A[M,K] W[N,K]^T), W streamed once straight into VGPRs (no LDS round trip), one 16-row W tile per
+//    block, the K range split over the block's 4 waves (and, where N has too few tiles to fill the chip, over KS blocks: fp32 slabs in a
+//    caller-owned workspace, summed in a fixed order by decode_gemm_combine_kernel).  Optional RMSNorm prologue (rstd of the <= 16 A rows
+//    computed by every block, gamma applied while A is loaded: vp_rmsnorm_fwd's rounding points), epilogues: none (bf16 / fp32 out),
+//    + residual, SwiGLU (act written directly).
+//  - decode_rope_append_kernel: rotate-half RoPE of q / k at per-sequence positions pos[b] (vp_rope's rounding points), k / v appended
+//    to row pos[b] of the cache.
+//  - decode_attn_split_kernel + decode_attn_combine_kernel: one query row per sequence, the Hq/Hkv heads of a KV head share every
+//    K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
+#include "common.h"
+
+#define VP_EPI_NONE 0
+#define VP_EPI_SWIGLU_IL 4      // SwiGLU on the interleaved gate|up rows (8 gate rows, 8 up rows, ...)
+#define VP_EPI_SWIGLU_HALVES 5  // SwiGLU on [gate | up] row halves
+
+static constexpr int DG_THREADS = 256;       // 4 waves
+static constexpr int DG_KCHUNK = 256;        // K elements one wave consumes per iteration: 4 lane groups x 64
+static constexpr int DG_TARGET_BLOCKS = 512; // grid the K split aims for (2 blocks per CU on 256 CUs)
+
+struct DecGemmArgs {
+  const bf16_t* A; const bf16_t* W; void* C; const bf16_t* res; const bf16_t* gamma;
+  float* ws;
+  int M, N, K, Kc, epi, out_f32, KS;
+  long lda, ldw, ldc, ldr;
+  float eps;
+};
+
+// split-K factor: a pure function of the shape (the workspace size query and the launch agree; results do not depend on the device)
+static int dg_ksplit(int N, int K, int epi) {
+  const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
+  int ks = 1;
+  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG_KCHUNK) == 0) ks *= 2;
+  return ks;
+}
+
+// W row that row r (0..15) of tile t reads
+__device__ __forceinline__ int dg_row(const DecGemmArgs& p, int t, int r) {
+  if (p.epi == VP_EPI_SWIGLU_HALVES) return r < 8 ? 8 * t + r : (p.N >> 1) + 8 * t + r - 8;
+  return 16 * t + r;
+}
+
+__device__ __forceinline__ bf16x8 dg_norm(bf16x8 a, const bf16_t* g, float rs) {
+  const bf16x8 gv = *(const bf16x8*)g;
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (short)f2bf(bf2f((bf16_t)gv[j]) * bfround(bf2f((bf16_t)a[j]) * rs));
+  return o;
+}
+
+// epilogue of one output element: v = fp32 sum (gate sum for SwiGLU), u = up sum (SwiGLU only); n = output column
+__device__ __forceinline__ void dg_store(const DecGemmArgs& p, int m, int n, float v, float u) {
+  if (p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES) {
+    const float g = bfround(v), up = bfround(u);
+    ((bf16_t*)p.C)[(long)m * p.ldc + n] = f2bf(bfround(silu(g)) * up);
+    return;
+  }
+  if (p.out_f32) { ((float*)p.C)[(long)m * p.ldc + n] = v; return; }
+  if (p.res) v = bfround(v) + bf2f(p.res[(long)m * p.ldr + n]);
+  ((bf16_t*)p.C)[(long)m * p.ldc + n] = f2bf(v);
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(DG_THREADS) void decode_gemm_kernel(DecGemmArgs p) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16];
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  if (NORM) {
+    // rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical)
+    for (int m = w; m < p.M; m += 4) {
+      const bf16_t* ar = p.A + (long)m * p.lda;
+      float ss = 0.f;
+      for (int e = lane * 8; e < p.K; e += 512) {
+        const bf16x8 v = *(const bf16x8*)(ar + e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
+      }
+      ss = wave_sum(ss);
+      if (lane == 0) rstd_s[m] = rsqrtf(ss / (float)p.K + p.eps);
+    }
+    __syncthreads();
+  }
+  // rows past N / M are clamped to the last valid row: their results are never stored, so the hot loop needs no masks
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const int m = min(r, p.M - 1);
+  const bf16_t* wr = p.W + (long)n * p.ldw;
+  const bf16_t* ar = p.A + (long)m * p.lda;
+  const float rs = NORM ? rstd_s[m] : 1.f;
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int c = kbeg + w * DG_KCHUNK; c < kend; c += 4 * DG_KCHUNK) {
+    const int k0 = c + g * 64;
+    bf16x8 wv[8], av[8];
+    if (c + DG_KCHUNK <= kend) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) wv[u] = __builtin_nontemporal_load((const bf16x8*)(wr + k0 + u * 8));
+#pragma unroll
+      for (int u = 0; u < 8; ++u) av[u] = *(const bf16x8*)(ar + k0 + u * 8);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool ok = k0 + u * 8 < kend;
+        const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        wv[u] = ok ? *(const bf16x8*)(wr + k0 + u * 8) : z;
+        av[u] = ok ? *(const bf16x8*)(ar + k0 + u * 8) : z;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (NORM) {
+        if (c + DG_KCHUNK <= kend || k0 + u * 8 < kend) av[u] = dg_norm(av[u], p.gamma + k0 + u * 8, rs);
+      }
+      // D[n][m] += sum_k W[n][k] A[m][k]: both operands carry the same k permutation (lane group g owns k0 .. k0 + 63)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[u], av[u], acc, 0, 0, 0);
+    }
+  }
+  // 4 waves -> one 16 x 16 tile, fixed order
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
+  __syncthreads();
+  {
+    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
+    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
+  }
+  __syncthreads();
+  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
+  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
+    const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+    const int nn = dg_row(p, t, nl);
+    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
+    return;
+  }
+  if (swiglu) {
+    if (threadIdx.x < 128) {
+      const int j = threadIdx.x >> 4, mm = threadIdx.x & 15;
+      if (mm < p.M) dg_store(p, mm, 8 * t + j, tile_s[j][mm], tile_s[j + 8][mm]);
+    }
+    return;
+  }
+  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm], 0.f);
+}
+
+// sums the KS slabs in order and applies the epilogue; one thread per output element
+__global__ __launch_bounds__(256) void decode_gemm_combine_kernel(DecGemmArgs p) {
+  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
+  const int nout = swiglu ? p.N / 2 : p.N;
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)p.M * nout) return;
+  const int m = (int)(i / nout), n = (int)(i % nout);
+  const long slab = (long)p.M * p.N;
+  if (swiglu) {
+    const int t = n >> 3, j = n & 7;
+    const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
+    float v = 0.f, u = 0.f;
+    for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
+    dg_store(p, m, n, v, u);
+    return;
+  }
+  float v = 0.f;
+  for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
+  dg_store(p, m, n, v, 0.f);
+}
+
+// ---------------------------------------------------------------- RoPE + KV append ---------------
+// qkv [B, ldq] rows (q heads | k heads | v heads); thread = one 8-wide vector of one head's first half (q / k) or 16 elements of v
+__global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo, long ldq,
+                                          bf16_t* __restrict__ kc, long k_bs, long k_ts, bf16_t* __restrict__ vc, long v_bs, long v_ts,
+                                          const float* __restrict__ cs, const float* __restrict__ sn, const int* __restrict__ pos,
+                                          int B, int Hq, int Hkv, int D, int Smax) {
+  const int half = D >> 1, vph = half >> 3;
+  const int per_b = (Hq + Hkv) * vph + Hkv * (D >> 3);
+  const long total = (long)B * per_b;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / per_b), r = (int)(i % per_b);
+    const int p = pos[b];
+    const bf16_t* row = qkv + (long)b * ldqkv;
+    if (r < (Hq + Hkv) * vph) {
+      const int h = r / vph, v = r % vph;
+      const bool isq = h < Hq;
+      if (!isq && (p < 0 || p >= Smax)) continue;               // never write outside the cache
+      const bf16_t* src = row + (long)h * D + v * 8;
+      const bf16x8 a = *(const bf16x8*)src, bb = *(const bf16x8*)(src + half);
+      const int pc = min(max(p, 0), Smax - 1);
+      const float* c = cs + (long)pc * half + v * 8;
+      const float* s = sn + (long)pc * half + v * 8;
+      bf16x8 oa, ob;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x1 = bf2f((bf16_t)a[j]), x2 = bf2f((bf16_t)bb[j]);
+        oa[j] = (short)f2bf(bfround(x1 * c[j]) + bfround(-x2 * s[j]));
+        ob[j] = (short)f2bf(bfround(x2 * c[j]) + bfround(x1 * s[j]));
+      }
+      bf16_t* dst = isq ? qo + (long)b * ldq + (long)h * D + v * 8 : kc + (long)b * k_bs + (long)p * k_ts + (long)(h - Hq) * D + v * 8;
+      *(bf16x8*)dst = oa;
+      *(bf16x8*)(dst + half) = ob;
+    } else {
+      if (p < 0 || p >= Smax) continue;
+      const int e = (r - (Hq + Hkv) * vph) * 8;                  // element within the Hkv * D v block
+      *(bf16x8*)(vc + (long)b * v_bs + (long)p * v_ts + e) = *(const bf16x8*)(row + (long)(Hq + Hkv) * D + e);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- decode attention ---------------
+static constexpr int DA_CHMAX = 512;       // keys one split block handles at most (scores stay in LDS)
+static constexpr float DA_LOG2E = 1.4426950408889634f;
+
+// grid (nsplit, Hkv, B), 256 threads.  Partial per (b, hkv, split, g): D unnormalised fp32 outputs, then m (log2 domain), l.
+template <int D, int G>
+__global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __restrict__ q, long q_bs, const bf16_t* __restrict__ k,
+                                                                long k_bs, long k_ts, const bf16_t* __restrict__ v, long v_bs, long v_ts,
+                                                                const int* __restrict__ kv_len, int Smax, int window, float scale,
+                                                                float* __restrict__ ws, int Hkv) {
+  constexpr int LPK = D <= 32 ? 4 : (D <= 64 ? 8 : 16);         // lanes per key row (16-byte vectors; D = 96 leaves 4 of 16 idle)
+  constexpr int KPB = 256 / LPK;                                 // key rows per block pass
+  __shared__ float sc[G][DA_CHMAX];
+  __shared__ float red[4][G][D];
+  __shared__ float ml[G][2];
+  const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int sl = tid % LPK, ko = tid / LPK, e = sl * 8;
+  const bool act = e < D;
+  const int len = min(kv_len[b], Smax);
+  const int lo = window > 0 ? max(0, len - window) : 0;
+  const int nk = max(0, len - lo);
+  const int ch = (nk + ns - 1) / ns;
+  const int s0 = lo + min(nk, s * ch), s1 = lo + min(nk, (s + 1) * ch);
+  const int cnt = s1 - s0;                                       // <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
+  float* out = ws + (((long)b * Hkv + hkv) * ns + s) * G * (D + 2);
+  float qf[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    bf16x8 qv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act) qv = *(const bf16x8*)(q + (long)b * q_bs + (long)(hkv * G + g) * D + e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[g][j] = bf2f((bf16_t)qv[j]) * (scale * DA_LOG2E);
+  }
+  const bf16_t* kb = k + (long)b * k_bs + (long)hkv * D + e;
+  const bf16_t* vb = v + (long)b * v_bs + (long)hkv * D + e;
+  // scores (log2 domain) -> LDS
+  for (int j0 = 0; j0 < cnt; j0 += KPB) {
+    const int j = j0 + ko;
+    bf16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act && j < cnt) kv = *(const bf16x8*)(kb + (long)(s0 + j) * k_ts);
+    float d[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float a = 0.f;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) a += qf[g][x] * bf2f((bf16_t)kv[x]);
+#pragma unroll
+      for (int o = LPK / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+      d[g] = a;
+    }
+    if (sl == 0 && j < cnt)
+#pragma unroll
+      for (int g = 0; g < G; ++g) sc[g][j] = d[g];
+  }
+  __syncthreads();
+  // per head: max, exp2, sum (wave w handles heads w, w + 4, ...)
+  for (int g = w; g < G; g += 4) {
+    float mx = -INFINITY;
+    for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, sc[g][j]);
+    mx = wave_max(mx);
+    float l = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+      const float pj = exp2f(sc[g][j] - mx);
+      sc[g][j] = pj;
+      l += pj;
+    }
+    l = wave_sum(l);
+    if (lane == 0) { ml[g][0] = mx; ml[g][1] = l; }
+  }
+  __syncthreads();
+  // P V
+  float acc[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int x = 0; x < 8; ++x) acc[g][x] = 0.f;
+  for (int j0 = 0; j0 < cnt; j0 += KPB) {
+    const int j = j0 + ko;
+    if (act && j < cnt) {
+      const bf16x8 vv = *(const bf16x8*)(vb + (long)(s0 + j) * v_ts);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float pj = sc[g][j];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) acc[g][x] += pj * bf2f((bf16_t)vv[x]);
+      }
+    }
+  }
+  // key groups of a wave (lanes sl, sl + LPK, ...) -> one, then the 4 waves in order
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int x = 0; x < 8; ++x)
+#pragma unroll
+      for (int o = LPK; o < 64; o <<= 1) acc[g][x] += __shfl_xor(acc[g][x], o, 64);
+  if (lane < LPK && act)
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) red[w][g][e + x] = acc[g][x];
+  __syncthreads();
+  for (int i = tid; i < G * D; i += 256) {
+    const int g = i / D, dd = i % D;
+    out[g * (D + 2) + dd] = ((red[0][g][dd] + red[1][g][dd]) + red[2][g][dd]) + red[3][g][dd];
+  }
+  if (tid < G) {
+    out[tid * (D + 2) + D] = cnt > 0 ? ml[tid][0] : -INFINITY;
+    out[tid * (D + 2) + D + 1] = cnt > 0 ? ml[tid][1] : 0.f;
+  }
+}
+
+// grid (Hq, B), D threads: o[b, h, :] = sum_s 2^(m_s - M) o_s / sum_s 2^(m_s - M) l_s, splits in order
+__global__ void decode_attn_combine_kernel(const float* __restrict__ ws, bf16_t* __restrict__ o, long o_bs, int Hkv, int G, int D,
+                                           int ns) {
+  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+  const int hkv = h / G, g = h % G;
+  const float* base = ws + ((long)b * Hkv + hkv) * ns * G * (D + 2) + (long)g * (D + 2);
+  const long sstride = (long)G * (D + 2);
+  float M = -INFINITY;
+  for (int s = 0; s < ns; ++s) M = fmaxf(M, base[s * sstride + D]);
+  float L = 0.f, acc = 0.f;
+  if (M != -INFINITY)
+    for (int s = 0; s < ns; ++s) {
+      const float ms = base[s * sstride + D];
+      if (ms == -INFINITY) continue;
+      const float f = exp2f(ms - M);
+      L += f * base[s * sstride + D + 1];
+      acc += f * base[s * sstride + d];
+    }
+  if (d < D) o[(long)b * o_bs + (long)h * D + d] = f2bf(L > 0.f ? acc / L : 0.f);
+}
+
+__global__ void add_i32_kernel(int* __restrict__ x, long n, int delta) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i < n) x[i] += delta;
+}
+
+extern "C" {
+
+int vp_add_i32(long n, int* x, int delta, hipStream_t stream) {
+  VP_REQUIRE(x && n > 0 && n <= (1L << 24), VP_ERR_BAD_ARG, "vp_add_i32: bad args (n = %ld)", n);
+  hipLaunchKernelGGL(add_i32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, n, delta);
+  return vp_check_launch("vp_add_i32");
+}
+
+long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const int ks = dg_ksplit(N, K, epilogue);
+  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
+}
+
+int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual,
+                   long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, hipStream_t stream) {
+  VP_REQUIRE(A && W && C, VP_ERR_BAD_ARG, "vp_decode_gemm: null A / W / C");
+  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm: M = %d (1 <= M <= 16; larger M: vp_gemm_bf16)", M);
+  VP_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm: N = %d, K = %d, lda = %ld, ldw = %ld (K, lda, ldw multiples of 8, lda / ldw >= K)", N, K, lda, ldw);
+  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm: A, W and norm_w must be 16-byte aligned");
+  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
+  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
+             epilogue);
+  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
+  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm: residual epilogue writes bf16 only");
+  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm: ldc / ldr too small");
+  const int ks = dg_ksplit(N, K, epilogue);
+  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm: this shape splits K %d ways and needs vp_decode_gemm_workspace_bytes() "
+             "of workspace (got NULL)", ks);
+  DecGemmArgs p{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
+                M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps};
+  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
+  if (norm_w)
+    hipLaunchKernelGGL(decode_gemm_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  else
+    hipLaunchKernelGGL(decode_gemm_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  if (ks > 1) {
+    const long nout = (long)M * (swiglu ? N / 2 : N);
+    hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
+  }
+  return vp_check_launch("vp_decode_gemm");
+}
+
+int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
+                          long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t, const int* pos, int Smax,
+                          hipStream_t stream) {
+  VP_REQUIRE(qkv && q_out && k_cache && v_cache && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "vp_decode_rope_append: null pointer");
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "vp_decode_rope_append: bad sizes");
+  VP_REQUIRE(D % 16 == 0 && ldqkv % 8 == 0 && ldq % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append: head_dim %d must be a multiple of 16, strides multiples of 8", D);
+  const long total = (long)B * ((Hq + Hkv) * (D / 16) + Hkv * (D / 8));
+  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
+                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, (bf16_t*)k_cache, k_bs, k_ts, (bf16_t*)v_cache, v_bs, v_ts,
+                     cos_t, sin_t, pos, B, Hq, Hkv, D, Smax);
+  return vp_check_launch("vp_decode_rope_append");
+}
+
+long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit) {
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || D <= 0 || nsplit <= 0) return 0;
+  return (long)B * Hq * nsplit * (D + 2) * (long)sizeof(float);
+}
+
+int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts, const void* v,
+                   long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
+                   hipStream_t stream) {
+  VP_REQUIRE(q && k && v && o && kv_len, VP_ERR_BAD_ARG, "vp_decode_attn: null pointer");
+  VP_REQUIRE(workspace, VP_ERR_BAD_ARG, "vp_decode_attn: workspace is NULL (vp_decode_attn_workspace_bytes)");
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Smax > 0 && window >= 0, VP_ERR_BAD_ARG,
+             "vp_decode_attn: bad sizes (B %d, Hq %d, Hkv %d, Smax %d)", B, Hq, Hkv, Smax);
+  const int G = Hq / Hkv;
+  VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: head_dim %d (32 | 64 | 96 | 128)", D);
+  VP_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: Hq / Hkv = %d (1 | 2 | 4 | 8)", G);
+  VP_REQUIRE(nsplit >= 1 && nsplit <= 1024 && (long)nsplit * DA_CHMAX >= Smax, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_attn: nsplit %d must cover Smax %d with at most %d keys per split", nsplit, Smax, DA_CHMAX);
+  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
+             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: strides must be multiples of 8 elements, bases 16-byte aligned");
+  const dim3 grid(nsplit, Hkv, B);
+#define DA_LAUNCH(DD, GG)                                                                                                             \
+  hipLaunchKernelGGL((decode_attn_split_kernel<DD, GG>), grid, dim3(256), 0, stream, (const bf16_t*)q, q_bs, (const bf16_t*)k, k_bs, \
+                     k_ts, (const bf16_t*)v, v_bs, v_ts, kv_len, Smax, window, scale, workspace, Hkv)
+#define DA_G(DD)                          \
+  switch (G) {                            \
+    case 1: DA_LAUNCH(DD, 1); break;      \
+    case 2: DA_LAUNCH(DD, 2); break;      \
+    case 4: DA_LAUNCH(DD, 4); break;      \
+    default: DA_LAUNCH(DD, 8); break;     \
+  }
+  switch (D) {
+    case 32: DA_G(32); break;
+    case 64: DA_G(64); break;
+    case 96: DA_G(96); break;
+    default: DA_G(128); break;
+  }
+#undef DA_G
+#undef DA_LAUNCH
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, G, D, nsplit);
+  return vp_check_launch("vp_decode_attn");
+}
+
+}  // extern "C"

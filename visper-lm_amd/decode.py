@@ -1,0 +1,257 @@
+"""KV-cached generation on the engine (the reference's `generate`: base_ola_vlm.py:579-616 for the PT classes, llava_llama.py:122 for the
+IFT classes — the multimodal splice, then HF's generation loop over `inputs_embeds`).
+
+  prefill   the label-less training forward (build_plan(labels=None) -> _embed -> _decoder_fwd(compute_grads=False)) with every layer's
+            post-RoPE k / v rows copied into the cache; lm_head on each sequence's last valid row only
+  step      per layer: QKV (RMSNorm prologue) -> RoPE + KV append at pos[b] -> decode attention -> wo + residual -> gate_up (RMSNorm
+            prologue, SwiGLU epilogue) -> down + residual; final norm folded into the fp32 lm_head launch; pos / kv_len += 1 on the device
+
+Every per-token scalar (token ids, positions, cache lengths) lives on the device, so one step can be captured once into a CUDA graph
+(single stream, no fork) and replayed for every token (VP_DECODE_GRAPH=1; the default is eager launches: capture did not pay, see below).  Decode reads the same kernel-ready weights
+_decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+BF16 = torch.bfloat16
+I32 = torch.int32
+
+
+class KVCache:
+    """Per layer one [B, Smax, 2 * Hkv * D] bf16 buffer: each token row is k (Hkv * D) | v (Hkv * D), the layout of the k|v columns of the fused
+    qkv rows (the prefill copies a sequence's rows in one strided copy).  `lens`: int32 [2B] on the device = (pos [B] = tokens cached,
+    kv_len [B] = pos + 1: the keys the next step attends to, its own included); `lens_host` mirrors pos."""
+
+    def __init__(self, cfg, B, Smax, device):
+        nkv, hd = cfg.num_key_value_heads, cfg.head_dim
+        self.B, self.Smax, self._hd = B, Smax, hd
+        self.kv = [torch.empty(B, Smax, 2 * nkv * hd, device=device, dtype=BF16) for _ in range(cfg.num_hidden_layers)]
+        self.lens = torch.zeros(2 * B, device=device, dtype=I32)
+        self.lens_host = np.zeros(B, np.int64)
+
+    def k(self, l):
+        B, Smax, C = self.kv[l].shape
+        return self.kv[l].view(B, Smax, 2, -1)[:, :, 0].unflatten(-1, (-1, self._hd))
+
+    def v(self, l):
+        B, Smax, C = self.kv[l].shape
+        return self.kv[l].view(B, Smax, 2, -1)[:, :, 1].unflatten(-1, (-1, self._hd))
+
+    @property
+    def pos(self):
+        return self.lens[:self.B]
+
+    @property
+    def kv_len(self):
+        return self.lens[self.B:]
+
+
+def text_plan(eng, input_ids, attention_mask):
+    """No-splice prefill input (text-only generate of the PT classes: base_ola_vlm.py:606-607 embeds the tokens as they are): each
+    sequence's valid tokens left-aligned in [B*S, H] rows gathered from the embedding table.  Returns (x, plan) with the plan fields
+    _decoder_fwd reads."""
+    ids = input_ids.detach().cpu().numpy().astype(np.int64)
+    am = np.ones_like(ids, dtype=bool) if attention_mask is None else attention_mask.detach().cpu().numpy().astype(bool)
+    B = ids.shape[0]
+    toks = [ids[b][am[b]] for b in range(B)]
+    V = eng.fz["embed"].shape[0]
+    bad = [int(t) for tk in toks for t in tk if not 0 <= t < V]
+    if bad:                                                      # (an <image> token without `images`, or an id outside the vocabulary)
+        raise ValueError(f"generate without images: prompt token ids must lie in [0, {V}), got {sorted(set(bad))[:4]}")
+    lens = np.array([len(t) for t in toks], np.int32)
+    if (lens == 0).any():
+        raise ValueError("generate: every sequence needs at least one prompt token")
+    S = int(lens.max())
+    kind = np.full((B, S), -1, np.int32)
+    row = np.zeros((B, S), np.int32)
+    for b, t in enumerate(toks):
+        kind[b, :len(t)] = 0
+        row[b, :len(t)] = t
+    dev = eng.dev
+    H = eng.cfg.hidden_size
+    x = torch.empty(B * S, H, device=dev, dtype=BF16)
+    ops.gather_rows([eng.fz["embed"]], torch.from_numpy(kind.reshape(-1)).to(dev), torch.from_numpy(row.reshape(-1)).to(dev), H, x)
+    plan = dict(B=B, S=S, lens_host=lens, full=bool((lens == S).all()), lens=torch.from_numpy(lens).to(dev), present=None)
+    return x, plan
+
+
+class DecodeSession:
+    """One generate() call: the cache, the preallocated step buffers and (optionally) the captured step."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.cfg = eng.cfg
+        self.graph = None
+        # capture measured on MI355X (profiles/decode_bench_*.json): no gain — the step is GPU-bound (Llama-3-8B B = 1: 9.01 ms/token
+        # replayed vs 9.06 eager, 3.3 ms of host enqueue under it), so eager launches are the default; VP_DECODE_GRAPH=1 captures
+        self.use_graph = os.environ.get("VP_DECODE_GRAPH", "0") == "1"
+        self.replays = 0
+
+    # ---------------------------------------------------------------------------------------------- prefill
+    def prefill(self, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=16):
+        """-> fp32 logits [B, V] of every sequence's last prompt position; the cache holds the prompt's k / v."""
+        eng, cfg = self.eng, self.cfg
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        if images is not None:
+            plan = eng.build_plan(input_ids, attention_mask, None, group_sizes)
+            x, *_ = eng._embed(images, plan)
+        else:
+            x, plan = text_plan(eng, input_ids, attention_mask)
+        B, S = plan["B"], plan["S"]
+        lens = np.asarray(plan["lens_host"]).astype(np.int64)
+        Smax = int(lens.max()) + int(max_new_tokens)
+        c = self.cache = KVCache(cfg, B, Smax, eng.dev)
+        cw = 2 * nkv * hd
+
+        def sink(l, qkv):
+            src = qkv.view(B, S, -1)
+            for b in range(B):                                  # rows 0 .. len_b - 1 (the kernels' layout is left-aligned for either padding side)
+                n = int(lens[b])
+                ops.copy2d_(c.kv[l][b, :n], src[b, :n, nh * hd:nh * hd + cw])
+
+        dec = eng._decoder_fwd(x, plan, compute_grads=False, kv_sink=sink)
+        H = cfg.hidden_size
+        last = torch.from_numpy((np.arange(B) * S + lens - 1).astype(np.int32)).to(eng.dev)
+        h_last = torch.empty(B, H, device=eng.dev, dtype=BF16)
+        ops.gather_rows([dec["hidden"]], torch.zeros(B, device=eng.dev, dtype=I32), last, H, h_last)
+        logits = ops.decode_gemm(h_last, eng.fz["lm_head"], out_f32=True)
+        c.lens.copy_(torch.from_numpy(np.concatenate([lens, lens + 1]).astype(np.int32)))
+        c.lens_host[:] = lens
+        self._alloc(B)
+        return logits
+
+    # ---------------------------------------------------------------------------------------------- step
+    def _alloc(self, B):
+        eng, cfg, dev = self.eng, self.cfg, self.eng.dev
+        H, I = cfg.hidden_size, cfg.intermediate_size
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        nqkv = (nh + 2 * nkv) * hd
+        V = eng.fz["lm_head"].shape[0]
+        e = lambda *shape, dt=BF16: torch.empty(*shape, device=dev, dtype=dt)
+        self.tok = torch.zeros(B, device=dev, dtype=I32)
+        self.zeros_b = torch.zeros(B, device=dev, dtype=I32)
+        self.x = [e(B, H), e(B, H)]
+        self.qkv, self.q, self.att, self.h1, self.act = e(B, nqkv), e(B, nh * hd), e(B, nh * hd), e(B, H), e(B, I)
+        self.logits = e(B, V, dt=torch.float32)
+        self.epi = ops.EPI_SWIGLU_IL if eng.gu_interleaved else ops.EPI_SWIGLU_HALVES
+        shapes = [(nqkv, H, 0), (H, nh * hd, 0), (2 * I, H, self.epi), (H, I, 0), (V, H, 0)]
+        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep) for N, K, ep in shapes)
+        self.gws = e(max(1, nb // 4), dt=torch.float32) if nb > 0 else None
+        Smax = self.cache.Smax
+        self.nsplit = ops.decode_attn_splits(B, nkv, Smax)
+        self.aws = e(ops._lib.raw("vp_decode_attn_workspace_bytes", B, nh, nkv, hd, self.nsplit) // 4, dt=torch.float32)
+        self.cos, self.sin = eng.rope(max(Smax, 1))
+
+    def _step_launches(self):
+        """The per-token launches (everything they read or write is preallocated: graph-capturable)."""
+        eng, cfg, fz, c = self.eng, self.cfg, self.eng.fz, self.cache
+        H, eps = cfg.hidden_size, cfg.rms_norm_eps
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        window = eng._attn_window()
+        x = self.x[0]
+        ops.gather_rows([fz["embed"]], self.zeros_b, self.tok, H, x)
+        for l in range(cfg.num_hidden_layers):
+            o = f"dec.{l}."
+            ops.decode_gemm(x, fz[o + "wqkv"], norm_w=fz[o + "ln1"], eps=eps, out=self.qkv, ws=self.gws)
+            ops.decode_rope_append(self.qkv, self.q, c.k(l), c.v(l), self.cos, self.sin, c.pos, nh, nkv, hd)
+            ops.decode_attn(self.q, c.k(l), c.v(l), c.kv_len, nh, window=window, nsplit=self.nsplit, out=self.att, ws=self.aws)
+            ops.decode_gemm(self.att, fz[o + "wo"], residual=x, out=self.h1, ws=self.gws)
+            ops.decode_gemm(self.h1, fz[o + "wgu"], norm_w=fz[o + "ln2"], eps=eps, epi=self.epi, out=self.act, ws=self.gws)
+            xn = self.x[(l + 1) % 2]
+            ops.decode_gemm(self.act, fz[o + "wd"], residual=self.h1, out=xn, ws=self.gws)
+            x = xn
+        ops.decode_gemm(x, fz["lm_head"], norm_w=fz["norm"], eps=eps, out_f32=True, out=self.logits, ws=self.gws)
+        ops.add_i32_(c.lens, 1)
+
+    def step(self, tokens):
+        """Feed one token per sequence (int tensor [B] on the device) -> fp32 logits [B, V] of the next position (a view of a buffer the next
+        step overwrites)."""
+        self.tok.copy_(tokens.to(I32))
+        if self.use_graph:
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+            self.replays += 1
+        else:
+            self._step_launches()
+        self.cache.lens_host += 1
+        return self.logits
+
+    def _capture(self):
+        """Capture _step_launches once (single stream, no fork).  Capture records without executing; `lens` moves only on replay."""
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.current_stream().synchronize()
+        with torch.cuda.graph(g):
+            self._step_launches()
+        self.graph = g
+
+
+# -------------------------------------------------------------------------------------------------- sampling (HF semantics, plain torch)
+def warp_logits(scores, temperature=1.0, top_p=1.0, min_tokens_to_keep=1):
+    """HF TemperatureLogitsWarper then TopPLogitsWarper (transformers/generation/logits_process.py) on fp32 [B, V] scores."""
+    if temperature is not None and temperature != 1.0:
+        scores = scores / temperature
+    if top_p is not None and top_p < 1.0:
+        sorted_logits, sorted_indices = torch.sort(scores, descending=False)
+        cumulative_probs = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
+        sorted_indices_to_remove = cumulative_probs <= (1 - top_p)
+        sorted_indices_to_remove[..., -min_tokens_to_keep:] = 0
+        indices_to_remove = sorted_indices_to_remove.scatter(1, sorted_indices, sorted_indices_to_remove)
+        scores = scores.masked_fill(indices_to_remove, -float("inf"))
+    return scores
+
+
+def next_tokens(logits, do_sample=False, temperature=1.0, top_p=1.0, generator=None):
+    if not do_sample:
+        return torch.argmax(logits, dim=-1)
+    probs = warp_logits(logits.float(), temperature, top_p).softmax(dim=-1)
+    return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
+
+
+def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=20, do_sample=False, temperature=1.0,
+             top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False):
+    """Greedy / sampled decoding of B prompts, each continuing at its own length -> LongTensor [B, n_new] of the new tokens only (rows that
+    finished are padded with pad_token_id after their EOS).  return_logits: also the fp32 logits [B, V] each token was chosen from."""
+    B = input_ids.shape[0]
+    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
+    if pad_token_id is None:
+        pad_token_id = eos[0] if eos else 0
+    sess = DecodeSession(eng)
+    if use_graph is not None:
+        sess.use_graph = bool(use_graph)
+    if streamer is not None:
+        streamer.put(input_ids.cpu())
+    with torch.no_grad():
+        logits = sess.prefill(input_ids, attention_mask, images, group_sizes, max_new_tokens)
+        dev = eng.dev
+        eos_t = torch.tensor(eos, device=dev, dtype=torch.long) if eos else None
+        finished = torch.zeros(B, device=dev, dtype=torch.bool)
+        out, kept = [], []
+        for i in range(int(max_new_tokens)):
+            if i > 0:
+                logits = sess.step(tok)
+            if return_logits:
+                kept.append(logits.clone())
+            raw = next_tokens(logits, do_sample, temperature, top_p, generator).to(torch.long)
+            nxt = torch.where(finished, torch.full_like(raw, pad_token_id), raw)
+            out.append(nxt)
+            if streamer is not None:
+                streamer.put(nxt.cpu())
+            if eos_t is not None:
+                finished = finished | torch.isin(nxt, eos_t)
+                if bool(finished.all()):
+                    break
+            tok = raw                                            # finished rows keep decoding their own (discarded) predictions: pad_token_id
+                                                                 # need not be a valid embedding row
+    if streamer is not None:
+        streamer.end()
+    res = torch.stack(out, 1) if out else torch.empty(B, 0, dtype=torch.long, device=eng.dev)
+    sess.graph = None
+    if return_logits:
+        return res, kept, sess
+    return res

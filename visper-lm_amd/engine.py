@@ -986,10 +986,11 @@ class Engine:
         return (t3[..., :nh * hd].view(B, S, nh, hd), t3[..., nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd),
                 t3[..., (nh + nkv) * hd:].view(B, S, nkv, hd))
 
-    def _decoder_fwd(self, x, plan, compute_grads):
+    def _decoder_fwd(self, x, plan, compute_grads, kv_sink=None):
         """a6: the decoder stack (ola_llama.py:105-119 -> HF LlamaModel / Phi3Model).  Returns the final pre-norm state, the normed hidden
         state, what the backward pass needs per layer, and the tapped layer states (layer_states[i] = output of layer i + 1, the last one
-        post-norm: ola_llama.py:117-119)."""
+        post-norm: ola_llama.py:117-119).  kv_sink(l, qkv): called with every layer's post-RoPE fused q|k|v rows [B*S, (nh + 2 nkv) hd]
+        (generation prefill: the KV cache takes its k / v rows; None = the training step's launches, unchanged)."""
         cfg, fz = self.cfg, self.fz
         B, S = plan["B"], plan["S"]
         M = B * S
@@ -1023,6 +1024,8 @@ class Engine:
                 else:                                       # D = 96: row-scaled GEMM (rope_cols = 0), then the rotation kernel
                     qkv = ops.gemm_rope(x, fz[o + "wqkv"], S, 0, cos_t, sin_t, row_scale=rstd1)
                     ops.rope_(qkv, M, S, nh + nkv, hd, cos_t, sin_t)
+                if kv_sink is not None:
+                    kv_sink(l, qkv)
                 q4, k4, v4 = self._qkv_views(qkv, B, S)
                 att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=window, kv_len=kv_len)
                 h1, part = ops.gemm_sumsq(att.view(M, nh * hd), fz[o + "wo"], x)
@@ -1047,6 +1050,8 @@ class Engine:
             else:
                 qkv = ops.gemm(xn, fz[o + "wqkv"])
                 ops.rope_(qkv, M, S, nh + nkv, hd, cos_t, sin_t)
+            if kv_sink is not None:
+                kv_sink(l, qkv)
             q4, k4, v4 = self._qkv_views(qkv, B, S)
             att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=window, kv_len=kv_len)
             h1 = ops.gemm(att.view(M, nh * hd), fz[o + "wo"], residual=x)

@@ -123,6 +123,40 @@ def _run_engine(module, eng, batch, labels, output_hidden_states, kwargs, force_
     return loss, out, logits, hidden_states
 
 
+def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
+              top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None, **kwargs):
+    """The reference's `generate` (base_ola_vlm.py:579-616 PT, llava_llama.py:122 IFT: the multimodal splice, then HF generation over
+    `inputs_embeds`), shared by the four mirrors: KV-cached decoding on the engine (decode.generate).  Returns a LongTensor [B, n_new] of
+    the NEW tokens only (what HF returns for an `inputs_embeds` call); finished rows are padded with pad_token_id after their EOS."""
+    from .. import decode
+    if num_beams is not None and int(num_beams) > 1:
+        raise NotImplementedError("num_beams > 1: beam search (HF generate, reached from base_ola_vlm.py:609-616) is not built; use num_beams=1")
+    for k in ("output_scores", "return_dict_in_generate"):
+        if kwargs.get(k):
+            raise NotImplementedError(f"{k}=True (HF generate's dict output, reached from base_ola_vlm.py:609-616) is not built: "
+                                      "generate returns the new token ids")
+    if kwargs.get("inputs_embeds") is not None:
+        raise NotImplementedError("inputs_embeds: base_ola_vlm.py:583-584 raises for it too (`inputs_embeds` is not supported)")
+    if inputs is None:
+        inputs = kwargs.get("input_ids")
+    if inputs is None:
+        raise ValueError("generate needs `inputs` (prompt token ids, base_ola_vlm.py:581)")
+    with torch.no_grad():
+        module._sync_trainable()
+        eng = module._get_engine()
+        gsz = None
+        if images is not None:
+            images, gsz = eng.image_groups(images)                   # list / 5-D images: flat merge; spatial / anyres refused there
+            images = images.to(eng.dev)
+        if eos_token_id is None:
+            eos_token_id = getattr(module.config, "eos_token_id", None)
+        if pad_token_id is None:
+            pad_token_id = getattr(module.config, "pad_token_id", None)
+        return decode.generate(eng, inputs, attention_mask, images, gsz, max_new_tokens=max_new_tokens, do_sample=do_sample,
+                               temperature=temperature, top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                               streamer=streamer, generator=generator)
+
+
 class _VisperStep(torch.autograd.Function):
     """One fused forward+backward on the engine; backward hands the already-computed gradients to autograd."""
 
@@ -491,6 +525,13 @@ class _OlaCausalLMBase(OlaLlavaMetaForCausalLM, BaseOLA_VLM, EngineModule):
         return res
 
     _forward = forward
+
+    def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
+                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None, **kwargs):
+        """base_ola_vlm.py:579-616: with `images` the prompt is spliced (image features + task tokens, ola_arch.py:256-444); with
+        images=None it is the token embeddings alone (base_ola_vlm.py:606-607).  -> LongTensor [B, n_new] (new tokens only)."""
+        return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
+                         pad_token_id, num_beams, use_cache, streamer, generator, **kwargs)
 
 
 class OlaLlavaLlamaForCausalLM(_OlaCausalLMBase):

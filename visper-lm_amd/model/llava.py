@@ -16,7 +16,7 @@ import torch
 
 from ..config import VisperConfig, phi3_mini
 from .builders import ParamTree
-from .language_model import EngineModule, _ModelOutput, _VisperStep, _run_engine
+from .language_model import EngineModule, _ModelOutput, _VisperStep, _generate, _run_engine
 from .ola_arch import OlaLlavaMetaForCausalLM, OlaLlavaMetaModel
 
 
@@ -149,6 +149,13 @@ class _LlavaCausalLMBase(LlavaMetaForCausalLM, EngineModule):
             res = CausalLMOutputWithPast(loss=loss, logits=logits)
             return tuple(v for v in (loss, res.logits, hidden_states if want_hs else None) if v is not None)
         return CausalLMOutputWithPast(loss=loss, logits=logits, hidden_states=hidden_states)
+
+    def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
+                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None, **kwargs):
+        """llava_llama.py:122-153: images -> prepare_inputs_labels_for_multimodal's splice, else the token embeddings alone; then HF
+        generation over inputs_embeds.  -> LongTensor [B, n_new] (new tokens only)."""
+        return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
+                         pad_token_id, num_beams, use_cache, streamer, generator, **kwargs)
 
 
 class LlavaLlamaForCausalLM(_LlavaCausalLMBase):

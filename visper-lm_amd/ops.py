@@ -649,3 +649,74 @@ def emb_loss_bwd_multi(preds, tgts, coefs, grad_outs, rank=0):
 
 def adamw_(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     _lib.call("vp_adamw", p.numel(), _p(p), _p(g), _p(m), _p(v), _p(shadow), lr, beta1, beta2, eps, wd, step, grad_scale, _stream())
+
+
+# ------------------------------------------------------------------------------------------------ single-token decode (generate)
+EPI_SWIGLU_IL, EPI_SWIGLU_HALVES = 4, 5
+
+
+def decode_gemm_ws_bytes(M, N, K, epi=EPI_NONE):
+    return int(_lib.raw("vp_decode_gemm_workspace_bytes", M, N, K, epi))
+
+
+def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f32=False, out=None, ws=None):
+    """out[M, N] = epi(norm(a)[M, K] @ w[N, K]^T) for M <= 16 (vp_decode_gemm): weight-streaming, optional RMSNorm prologue (gamma norm_w),
+    + residual, SwiGLU on the fused gate|up weight (epi EPI_SWIGLU_IL / EPI_SWIGLU_HALVES: out [M, N/2]), fp32 output (logits).
+    ws: caller-owned fp32 workspace of at least decode_gemm_ws_bytes() (allocated here when None)."""
+    M, K, lda = _rows2d(a)
+    N, K2, ldw = _rows2d(w)
+    assert K == K2 and a.dtype == BF16 and w.dtype == BF16, (a.shape, w.shape)
+    nout = N // 2 if epi in (EPI_SWIGLU_IL, EPI_SWIGLU_HALVES) else N
+    if out is None:
+        out = torch.empty(M, nout, device=a.device, dtype=torch.float32 if out_f32 else BF16)
+    _, _, ldc = _rows2d(out)
+    ldr = 0 if residual is None else _rows2d(residual)[2]
+    if ws is None:
+        nb = decode_gemm_ws_bytes(M, N, K, epi)
+        ws = torch.empty(max(1, nb // 4), device=a.device, dtype=torch.float32) if nb > 0 else None
+    _lib.call("vp_decode_gemm", M, N, K, _p(a), lda, _p(w), ldw, _p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps), int(epi),
+              1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
+    return out
+
+
+def decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv, D):
+    """RoPE of one new token per sequence at position pos[b] (int32 [B], device): q -> q_out [B, Hq*D]; k, v -> row pos[b] of the caches
+    ([B, Smax, Hkv, D] views whose (Hkv, D) block is contiguous)."""
+    B, _, ldqkv = _rows2d(qkv)
+    kb, kt = _bshd(k_cache)
+    vb, vt = _bshd(v_cache)
+    Smax = k_cache.shape[1]
+    assert cos_t.shape[0] >= Smax and pos.dtype == torch.int32 and pos.numel() == B
+    _lib.call("vp_decode_rope_append", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out), q_out.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt,
+              _p(cos_t), _p(sin_t), _p(pos), Smax, _stream())
+    return q_out
+
+
+def decode_attn_splits(B, Hkv, Smax, cus=256):
+    """Key-range splits of vp_decode_attn: B * Hkv * splits >= 2 blocks per CU, each split at most 512 keys."""
+    ns = max(1, -(-2 * cus // (B * Hkv)))
+    return min(1024, max(ns, -(-Smax // 512)))
+
+
+def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+    """q [B, Hq*D] rows, caches [B, Smax, Hkv, D], kv_len int32 [B] (device) -> o [B, Hq*D] bf16."""
+    B, Smax, Hkv, D = k_cache.shape
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if nsplit is None:
+        nsplit = decode_attn_splits(B, Hkv, Smax)
+    if out is None:
+        out = torch.empty(B, Hq * D, device=q.device, dtype=BF16)
+    if ws is None:
+        ws = torch.empty(_lib.raw("vp_decode_attn_workspace_bytes", B, Hq, Hkv, D, nsplit) // 4, device=q.device, dtype=torch.float32)
+    kb, kt = _bshd(k_cache)
+    vb, vt = _bshd(v_cache)
+    _lib.call("vp_decode_attn", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt, _p(out), out.stride(0),
+              _p(kv_len), int(window), float(scale), int(nsplit), _p(ws), _stream())
+    return out
+
+
+def add_i32_(x, delta=1):
+    assert x.dtype == torch.int32 and x.is_contiguous()
+    _lib.call("vp_add_i32", x.numel(), _p(x), int(delta), _stream())
+    return x
