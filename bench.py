@@ -10,7 +10,13 @@ fwd/bwd + embedding losses + (N>1: RCCL grad all-reduce, contrastive target all-
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the bf16 MFMA
-GEMM, timed live with HIP events on its launch stream) and `cpu_baseline` (the CPU oracle timed on a bounded sample).
+GEMM, timed live with HIP events on its launch stream inside the timed steps).  A plain run does only what that line
+needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  `--full` adds everything that takes runs of its own
+after the timed region: the one-stream schedule, the K11 and shader-clock probes, `extras` (secondary legs in fresh
+processes) and `cpu_baseline` (the CPU oracle timed on a bounded sample).  With N > 1 ranks the line's `multi_gpu`
+self-diagnosis runs either way: the headline value is taken from one of its transport legs.
+
+  python bench.py --full --steps 5 --warmup 2
 """
 import argparse
 import json
@@ -117,15 +123,15 @@ def cpu_baseline(cfg, dev):
 
 
 def run_extras(args, headline_ms, step_tf_hint=None):
-    """Secondary legs of the default line, each a FRESH process of this script started after the headline's timed region (this process has
-    freed the GPU by then): W = 2 warm-up + K = --extras-steps timed steps between the same barrier + synchronize fences, every other probe
-    off.  engine_direct = Engine.train_step / optimizer_step without the model class (rounds 1-5's headline); reference_outputs = the model
+    """Secondary legs of the --full line, each a FRESH process of this script started after the headline's timed region (this process has
+    freed the GPU by then): W = 2 warm-up + K = --extras-steps timed steps between the same barrier + synchronize fences, a plain run (no
+    probes).  engine_direct = Engine.train_step / optimizer_step without the model class (rounds 1-5's headline); reference_outputs = the model
     class with its contract default config.reference_outputs=True (all L + 1 layer states returned, fp32 logits of all B x S rows handed out
     lazily: ola_llama.py:113-122) driven as a trainer drives it (reads .loss); ..._logits_read = the same with out.logits read every step;
     configs[4] / configs[3] = the other two single-GPU configurations of BASELINE.json through the model class."""
     import subprocess
-    base = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.extras_steps), "--warmup", "2", "--no-probes",
-            "--no-cpu-baseline", "--no-extras", "--lr", str(args.lr)] + (["--no-depth-decoder"] if args.no_depth_decoder else [])
+    base = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.extras_steps), "--warmup", "2",
+            "--lr", str(args.lr)] + (["--no-depth-decoder"] if args.no_depth_decoder else [])
     legs = [("engine_direct", ["--api", "engine"]), ("reference_outputs", ["--api", "model", "--reference-outputs"]),
             ("reference_outputs_logits_read", ["--api", "model", "--reference-outputs", "--read-logits"]),
             ("configs[4]_phi3", ["--api", "model", "--workload", "phi3"]), ("configs[3]_convnext", ["--api", "model", "--workload", "convnext"])]
@@ -482,8 +488,11 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--text-len", type=int, default=1449)          # -> post-splice S = 2048 with 3 tasks
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer decoder layers (result marked invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probes", action="store_true", help="skip the stand-alone K11 / shader-clock probes (profiling runs: keeps their launches out of the kernel stats)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run what takes runs of its own: the one-stream schedule, the K11 / shader-clock "
+                         "probes, extras and the CPU baseline; a plain run does only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: skip the one-stream schedule and the stand-alone K11 / shader-clock probes")
     ap.add_argument("--no-depth-decoder", action="store_true",
                     help="skip the frozen DPT depth decoder (depth_preds: a logging-only output the reference computes under no_grad in "
                          "every training step, base_ola_vlm.py:462-470; ~6 ms/step here); on by default so the timed step does all the "
@@ -502,9 +511,9 @@ def main():
                     help="model (default) = the drop-in boundary north_star names: every step is `out = model(**batch); out.loss.backward(); "
                          "model.optimizer_step(lr)` through the reference-named class (OlaLlavaLlamaForCausalLM / OlaLlavaPhi3ForCausalLM / "
                          "LlavaLlamaForCausalLM: ola_vlm_train.py:1297-1327 -> ola_llama.py:190-244); engine = Engine.train_step + "
-                         "Engine.optimizer_step called directly (what rounds 1-5 timed; reported beside the headline under `extras`)")
+                         "Engine.optimizer_step called directly (what rounds 1-5 timed; reported beside the headline under `extras` with --full)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary legs of the default line (engine-direct, reference outputs, configs[4] phi3, configs[3] convnext: each a "
+                    help="with --full: skip the secondary legs (engine-direct, reference outputs, configs[4] phi3, configs[3] convnext: each a "
                          "fresh process of this script after the timed region, a few steps between the same fences)")
     ap.add_argument("--extras-steps", type=int, default=3)
     ap.add_argument("--read-logits", action="store_true",
@@ -769,7 +778,8 @@ def main():
                         "durations include whatever CU-time the side stream took"}
     # The same launches with the step on ONE stream (3 extra steps outside the timed region, world 1 only): what the kernel does when nothing shares
     # the chip with it — the figure the earlier rounds' `frac` was.
-    if dist is None and not args.no_probes and os.environ.get("VP_HEADS_STREAM", "1") != "0":
+    probes = args.full and not args.no_probes
+    if dist is None and probes and os.environ.get("VP_HEADS_STREAM", "1") != "0":
         keep = {k: os.environ.get(k) for k in ("VP_HEADS_STREAM", "VP_TOWER_STREAM")}
         os.environ["VP_HEADS_STREAM"], os.environ["VP_TOWER_STREAM"] = "0", "0"
         try:
@@ -821,7 +831,7 @@ def main():
                                       "default config.reference_outputs=True)" % ("READ every step" if args.read_logits else "handed out lazily, not read")
                                       if args.reference_outputs
                                       else "lean: loss + per-layer losses + embeddings (config.reference_outputs=False: no logits tensor, lm_head + CE on "
-                                           "labelled rows only; the contract-default mode is timed under extras.reference_outputs)"),
+                                           "labelled rows only; the contract-default mode is timed under extras.reference_outputs with --full)"),
                           "valid": args.layers is None},
                "roofline": roof, **({"multi_gpu": diag} if diag is not None else {})}
 
@@ -846,21 +856,21 @@ def main():
     if rank == 0:
         res = assemble()
         # the stand-alone probes run AFTER the timed region and must never cost the line: a failing probe is reported as its error string
-        if args.workload in ("llama3_8b", "convnext", "phi3", "pt6") and not args.no_probes:
+        if args.workload in ("llama3_8b", "convnext", "phi3", "pt6") and probes:
             try:
                 roof["k11"] = {"what": "distillation-loss reduction vp_emb_loss_fwd/bwd alone: 25 back-to-back launches in a HIP graph, replayed (N > 1: a python loop), HIP events on its stream, per launch (launch gap included)",
                                "peak_GBps": 8000.0, "world1": k11_probe(cfg, args.batch, 1, dev), "world8_shaped": k11_probe(cfg, args.batch, 8, dev)}
             except Exception as e:                      # noqa: BLE001
                 roof["k11"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         # the chip clocks to its 1400 W package cap: the 2.5 PFLOP/s peak assumes 2.4 GHz; report the clock the kernel actually sustains
-        if not args.no_probes:
+        if probes:
             try:
                 ck = clock_probe(dev)
                 roof["clock"] = ck
                 roof["frac_at_sustained_clock"] = round(achieved / (PEAK_BF16_TF * ck["shader_clock_mhz"] / ck["nominal_mhz"]), 4)
             except Exception as e:                      # noqa: BLE001
                 roof["clock"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and args.workload == "llama3_8b" and (not args.no_extras or not args.no_cpu_baseline):
+        if args.full and world == 1 and args.workload == "llama3_8b" and (not args.no_extras or not args.no_cpu_baseline):
             del eng, fresh, pool, model, out
             import gc
             gc.collect()
