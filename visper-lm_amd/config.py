@@ -49,6 +49,9 @@ class VisperConfig:
             grad_reduce_dtype="bf16",   # DP gradient buckets on the wire: "bf16" (the reference's ZeRO-2 reduces bf16 gradients) | "fp32"
             train_llm=False,       # True = IFT-stage trainability: the whole LLM gets weight gradients + AdamW
             depth_decoder=False,   # True also runs the frozen DPT decoder on every depth head (base_ola_vlm.py:462-470 -> depth_preds)
+            # False | "full" (= True) | "keep_attn": the decoder backward recomputes each layer from its input instead of keeping the layer's
+            # activations ("keep_attn" keeps the attention output too and skips that kernel in the recompute); bit-identical gradients
+            gradient_checkpointing=False,
         )
         d.update(kw)
         if "mm_hidden_size" not in kw:

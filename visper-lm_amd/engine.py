@@ -14,8 +14,8 @@ of the reference's hot path entirely through the C ABI (o
 
 Data layout in HBM (sized for 288 GB): frozen decoder weights are kept twice — [out,in] for forward and
 the pre-transposed [in,out] copy for dgrad — so both directions run the same K-contiguous MFMA GEMM;
-q/k/v and gate/up are fused into single weights; activations needed by backward are kept (no recompute:
-~1.5 GB/layer at B=8,S=2048).  Trainable parameters live in one flat fp32 master buffer (+ bf16 shadow,
+q/k/v and gate/up are fused into single weights; activations needed by backward are kept (~1.5 GB/layer
+at B=8,S=2048) unless Engine.gradient_checkpointing makes the backward recompute each layer from its input.  Trainable parameters live in one flat fp32 master buffer (+ bf16 shadow,
 fp32 grads, Adam moments) so the DP all-reduce and the fused AdamW are one launch each.
 """
 from __future__ import annotations
@@ -23,7 +23,7 @@ from __future__ import annotations
 import os
 
 import math
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -40,6 +40,12 @@ TASK_SPEC = {   # task -> (config attr, layer key, weight key, logit-scale name,
     "seg": ("image_seg", "seg_layer_indices", "seg_loss_weight", "seg_logit_scale", "image_seg_heads"),
     "gen": ("image_gen", "img_layer_indices", "img_loss_weight", "gen_logit_scale", "image_gen_heads"),
 }
+
+
+CKPT_MODES = ("full", "keep_attn")      # Engine.gradient_checkpointing (besides False; True = "full")
+# What a checkpointed decoder layer keeps for the backward pass: its input and that input's 1/rms (both alive anyway as the previous
+# layer's output), and in "keep_attn" mode the attention output + log-sum-exp (None in "full" mode).
+_Ckpt = namedtuple("_Ckpt", "x rstd1 att lse")
 
 
 def is_trainable(name: str, train_llm: bool = False) -> bool:
@@ -176,6 +182,9 @@ class Engine:
         self.keep_logits = False
         self.lm_head_all_rows = False # True: no labelled-row compaction — every row through lm_head + CE + the d_hidden GEMM, literally as ola_llama.py:121-136 (A/B + test aid)
         self.keep_states = False      # True: train_step also returns every decoder-layer state (HF `hidden_states`: embeddings, layer outputs, final norm)
+        # False | "full" (= True) | "keep_attn": the decoder backward recomputes each layer's forward from its checkpointed input instead of
+        # reading stored activations (_decoder_fwd / _decoder_bwd); may be changed between steps
+        self.gradient_checkpointing = getattr(cfg, "gradient_checkpointing", False)
 
     def _load_frozen_decoder(self, W, d):
         """PT stage: the LLM is frozen -> bf16 kernel-ready copies, q/k/v and gate/up fused, plus pre-transposed dgrad copies."""
@@ -986,93 +995,133 @@ class Engine:
         return (t3[..., :nh * hd].view(B, S, nh, hd), t3[..., nh * hd:(nh + nkv) * hd].view(B, S, nkv, hd),
                 t3[..., (nh + nkv) * hd:].view(B, S, nkv, hd))
 
-    def _decoder_fwd(self, x, plan, compute_grads, kv_sink=None):
-        """a6: the decoder stack (ola_llama.py:105-119 -> HF LlamaModel / Phi3Model).  Returns the final pre-norm state, the normed hidden
-        state, what the backward pass needs per layer, and the tapped layer states (layer_states[i] = output of layer i + 1, the last one
-        post-norm: ola_llama.py:117-119).  kv_sink(l, qkv): called with every layer's post-RoPE fused q|k|v rows [B*S, (nh + 2 nkv) hd]
-        (generation prefill: the KV cache takes its k / v rows; None = the training step's launches, unchanged)."""
-        cfg, fz = self.cfg, self.fz
+    def _ckpt_mode(self):
+        """Engine.gradient_checkpointing as one of False | "full" | "keep_attn" (True means "full")."""
+        m = self.gradient_checkpointing
+        if m is True:
+            return "full"
+        if not m:
+            return False
+        if m not in CKPT_MODES:
+            raise ValueError(f"gradient_checkpointing={m!r}: expected False, True, 'full' or 'keep_attn'")
+        return m
+
+    def _decoder_decisions(self, plan):
+        """What every decoder layer of ONE step shares: shapes, RoPE tables, the attention mask arguments and which fused kernels the shape
+        allows.  Taken once per step (_decoder_fwd) and handed to the backward pass, so that a layer recomputed there (gradient
+        checkpointing) launches exactly what its first forward launched."""
+        cfg = self.cfg
         B, S = plan["B"], plan["S"]
         M = B * S
         nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         cos_t, sin_t = self.rope(S)
-        kv_len = None if plan["full"] else plan["lens"]
-        window = self._attn_window()
-        L = cfg.num_hidden_layers
-        saved, states = [], {}
         il = self.gu_interleaved
         fuse = il and ops.swiglu_fusable(M, 2 * cfg.intermediate_size, cfg.hidden_size) and \
             ops.swiglu_fusable(M, cfg.intermediate_size, cfg.hidden_size)
         fuse_rope = ops.gemm_rope_ok(M, (nh + 2 * nkv) * hd, cfg.hidden_size, hd) and cos_t.shape[-1] == 64
         fold = getattr(self, "fold_norm", False) and not self.train_llm and fuse and (fuse_rope or hd == 96) and \
             ops.fold_norm_ok(M, cfg.hidden_size, cfg.intermediate_size, hd, (nh + 2 * nkv) * hd)
-        self.last_fold = bool(fold)                      # (which set of rounding points the last step took: DESIGN section 2, deviation v)
+        return dict(B=B, S=S, M=M, cos_t=cos_t, sin_t=sin_t, kv_len=None if plan["full"] else plan["lens"], window=self._attn_window(),
+                    il=il, fuse=fuse, fuse_rope=fuse_rope, fold=bool(fold))
+
+    def _layer_fwd(self, l, x, rstd1, dc, kv_sink=None, ckpt=None):
+        """Decoder layer l on the stream x [M, H] (folded-norm branch: rstd1 = 1/rms of x's rows, out of the previous layer's down
+        projection; None for layer 0 and in the plain branch, which computes it).  Returns (saved, xo, rnext): the tuple the backward
+        pass reads (x, rstd1, qkv, att, lse, h1, rstd2, gu), the layer's output and, in the folded branch, its 1/rms (None for the last
+        layer).  ckpt = this layer's _Ckpt: the RECOMPUTE of the backward pass — same kernels, same arguments, hence the same bits —
+        which stops in front of the down projection (its result is the next layer's checkpointed input: xo = rnext = None) and skips
+        the attention forward when the checkpoint kept att / lse."""
+        cfg, fz = self.cfg, self.fz
+        B, S, M = dc["B"], dc["S"], dc["M"]
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        cos_t, sin_t = dc["cos_t"], dc["sin_t"]
         H, eps = cfg.hidden_size, cfg.rms_norm_eps
-        rstd1 = None
-        hs = [] if self.keep_states else None            # HF all_hidden_states: the input of every layer, then the post-norm final state
-        for l in range(L):
-            o = f"dec.{l}."
-            if hs is not None:
-                hs.append(x)
-            if fold:
-                # no normalised copy of the stream: 1/rms rides in the consuming GEMM's epilogue (gamma is in its weight), the statistics of the next
-                # norm come out of the residual GEMM that writes the stream (layer 0's from one pass over the spliced embeddings)
-                if rstd1 is None:
-                    _, rstd1 = ops.rmsnorm_fwd(x, fz["ones_h"], eps)
-                if fuse_rope:
-                    qkv = ops.gemm_rope(x, fz[o + "wqkv"], S, (nh + nkv) * hd, cos_t, sin_t, row_scale=rstd1)
-                else:                                       # D = 96: row-scaled GEMM (rope_cols = 0), then the rotation kernel
-                    qkv = ops.gemm_rope(x, fz[o + "wqkv"], S, 0, cos_t, sin_t, row_scale=rstd1)
-                    ops.rope_(qkv, M, S, nh + nkv, hd, cos_t, sin_t)
-                if kv_sink is not None:
-                    kv_sink(l, qkv)
-                q4, k4, v4 = self._qkv_views(qkv, B, S)
-                att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=window, kv_len=kv_len)
-                h1, part = ops.gemm_sumsq(att.view(M, nh * hd), fz[o + "wo"], x)
-                rstd2 = ops.rstd_from_sumsq(part, H, eps)
-                gu, act = ops.gemm_swiglu_fwd(h1, fz[o + "wgu"], row_scale=rstd2)
-                if l == L - 1:
-                    xo = ops.gemm(act, fz[o + "wd"], residual=h1)
-                    rnext = None
-                else:
-                    xo, part = ops.gemm_sumsq(act, fz[o + "wd"], h1)
-                    rnext = ops.rstd_from_sumsq(part, H, eps)
-                del part
-                if compute_grads:
-                    saved.append((x, rstd1, qkv, att, lse, h1, rstd2, gu))
-                if l in self.tapped and l != L - 1:
-                    states[l] = xo
-                x, rstd1 = xo, rnext
-                continue
-            xn, rstd1 = ops.rmsnorm_fwd(x, fz[o + "ln1"], cfg.rms_norm_eps)
-            if fuse_rope:                                       # RoPE of q and k in the QKV GEMM's epilogue (bit-identical to gemm + rope_)
-                qkv = ops.gemm_rope(xn, fz[o + "wqkv"], S, (nh + nkv) * hd, cos_t, sin_t)
-            else:
-                qkv = ops.gemm(xn, fz[o + "wqkv"])
+        L = cfg.num_hidden_layers
+        o = f"dec.{l}."
+        att, lse = (ckpt.att, ckpt.lse) if ckpt is not None else (None, None)
+        if dc["fold"]:
+            # no normalised copy of the stream: 1/rms rides in the consuming GEMM's epilogue (gamma is in its weight), the statistics of the next
+            # norm come out of the residual GEMM that writes the stream (layer 0's from one pass over the spliced embeddings)
+            if rstd1 is None:
+                _, rstd1 = ops.rmsnorm_fwd(x, fz["ones_h"], eps)
+            if dc["fuse_rope"]:
+                qkv = ops.gemm_rope(x, fz[o + "wqkv"], S, (nh + nkv) * hd, cos_t, sin_t, row_scale=rstd1)
+            else:                                       # D = 96: row-scaled GEMM (rope_cols = 0), then the rotation kernel
+                qkv = ops.gemm_rope(x, fz[o + "wqkv"], S, 0, cos_t, sin_t, row_scale=rstd1)
                 ops.rope_(qkv, M, S, nh + nkv, hd, cos_t, sin_t)
             if kv_sink is not None:
                 kv_sink(l, qkv)
+            if att is None:
+                q4, k4, v4 = self._qkv_views(qkv, B, S)
+                att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=dc["window"], kv_len=dc["kv_len"])
+            h1, part = ops.gemm_sumsq(att.view(M, nh * hd), fz[o + "wo"], x)
+            rstd2 = ops.rstd_from_sumsq(part, H, eps)
+            gu, act = ops.gemm_swiglu_fwd(h1, fz[o + "wgu"], row_scale=rstd2)
+            saved = (x, rstd1, qkv, att, lse, h1, rstd2, gu)
+            if ckpt is not None:
+                return saved, None, None
+            if l == L - 1:
+                return saved, ops.gemm(act, fz[o + "wd"], residual=h1), None
+            xo, part = ops.gemm_sumsq(act, fz[o + "wd"], h1)
+            return saved, xo, ops.rstd_from_sumsq(part, H, eps)
+        xn, rstd1 = ops.rmsnorm_fwd(x, fz[o + "ln1"], eps)
+        if dc["fuse_rope"]:                                     # RoPE of q and k in the QKV GEMM's epilogue (bit-identical to gemm + rope_)
+            qkv = ops.gemm_rope(xn, fz[o + "wqkv"], S, (nh + nkv) * hd, cos_t, sin_t)
+        else:
+            qkv = ops.gemm(xn, fz[o + "wqkv"])
+            ops.rope_(qkv, M, S, nh + nkv, hd, cos_t, sin_t)
+        if kv_sink is not None:
+            kv_sink(l, qkv)
+        if att is None:
             q4, k4, v4 = self._qkv_views(qkv, B, S)
-            att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=window, kv_len=kv_len)
-            h1 = ops.gemm(att.view(M, nh * hd), fz[o + "wo"], residual=x)
-            hn, rstd2 = ops.rmsnorm_fwd(h1, fz[o + "ln2"], cfg.rms_norm_eps)
-            if fuse:
-                gu, act = ops.gemm_swiglu_fwd(hn, fz[o + "wgu"])
-            else:
-                gu = ops.gemm(hn, fz[o + "wgu"])
-                act = ops.swiglu_fwd(gu, interleaved=il)
-            xo = ops.gemm(act, fz[o + "wd"], residual=h1)
+            att, lse = ops.attn_fwd(q4, k4, v4, causal=True, window=dc["window"], kv_len=dc["kv_len"])
+        h1 = ops.gemm(att.view(M, nh * hd), fz[o + "wo"], residual=x)
+        hn, rstd2 = ops.rmsnorm_fwd(h1, fz[o + "ln2"], eps)
+        if dc["fuse"]:
+            gu, act = ops.gemm_swiglu_fwd(hn, fz[o + "wgu"])
+        else:
+            gu = ops.gemm(hn, fz[o + "wgu"])
+            act = None if ckpt is not None else ops.swiglu_fwd(gu, interleaved=dc["il"])
+        saved = (x, rstd1, qkv, att, lse, h1, rstd2, gu)
+        if ckpt is not None:
+            return saved, None, None
+        return saved, ops.gemm(act, fz[o + "wd"], residual=h1), None
+
+    def _decoder_fwd(self, x, plan, compute_grads, kv_sink=None):
+        """a6: the decoder stack (ola_llama.py:105-119 -> HF LlamaModel / Phi3Model).  Returns the final pre-norm state, the normed hidden
+        state, what the backward pass needs per layer, and the tapped layer states (layer_states[i] = output of layer i + 1, the last one
+        post-norm: ola_llama.py:117-119).  kv_sink(l, qkv): called with every layer's post-RoPE fused q|k|v rows [B*S, (nh + 2 nkv) hd]
+        (generation prefill: the KV cache takes its k / v rows; None = the training step's launches, unchanged).
+        Kept per layer for the backward pass: everything it reads (gradient_checkpointing off), or a _Ckpt — the layer's input and its
+        1/rms ("full"), plus the attention output and its log-sum-exp ("keep_attn") — from which _decoder_bwd recomputes the rest."""
+        cfg, fz = self.cfg, self.fz
+        L = cfg.num_hidden_layers
+        saved, states = [], {}
+        dc = self._decoder_decisions(plan)
+        self.last_fold = dc["fold"]                      # (which set of rounding points the last step took: DESIGN section 2, deviation v)
+        mode = self._ckpt_mode() if compute_grads else False
+        rstd1 = None
+        hs = [] if self.keep_states else None            # HF all_hidden_states: the input of every layer, then the post-norm final state
+        for l in range(L):
+            if hs is not None:
+                hs.append(x)
+            sv, xo, rnext = self._layer_fwd(l, x, rstd1, dc, kv_sink)
             if compute_grads:
-                saved.append((x, rstd1, qkv, att, lse, h1, rstd2, gu))
+                if mode == "full":
+                    sv = _Ckpt(sv[0], sv[1], None, None)
+                elif mode == "keep_attn":
+                    sv = _Ckpt(sv[0], sv[1], sv[3], sv[4])
+                saved.append(sv)
+            del sv
             if l in self.tapped and l != L - 1:
                 states[l] = xo
-            x = xo
+            x, rstd1 = xo, rnext
         hidden, rstd_f = ops.rmsnorm_fwd(x, fz["norm"], cfg.rms_norm_eps)
         if (L - 1) in self.tapped:
             states[L - 1] = hidden              # layer_states[-1] is the post-norm state (ola_llama.py:117-119)
         if hs is not None:
             hs.append(hidden)
-        return dict(x=x, hidden=hidden, rstd_f=rstd_f, saved=saved, states=states, hidden_states=hs)
+        return dict(x=x, hidden=hidden, rstd_f=rstd_f, saved=saved, states=states, hidden_states=hs, dc=dc)
 
     def _lm_chunk(self, Mc, H):
         """Rows per lm_head chunk: whole 256-row tiles, at most lm_chunk_rows (the bf16 logits of a chunk are the step's largest transient:
@@ -1269,7 +1318,11 @@ class Engine:
         del d_hidden
         for l in range(L - 1, -1, -1):
             o = f"dec.{l}."
-            x_in, rstd1, qkv, att, lse, h1, rstd2, gu = saved[l]
+            sv = saved[l]
+            if isinstance(sv, _Ckpt):            # gradient checkpointing: this layer's forward again, from its kept input (one layer's set alive at a time)
+                sv, _, _ = self._layer_fwd(l, sv.x, sv.rstd1, dec["dc"], ckpt=sv)
+            x_in, rstd1, qkv, att, lse, h1, rstd2, gu = sv
+            del sv
             if l in d_state and l != L - 1:
                 self._join_heads()
                 ops.add(dx, d_state[l], out=dx)
@@ -1312,6 +1365,8 @@ class Engine:
                 self._reduce_range(*self._llm_ranges[o])        # this layer's gradients are final
             dx = ops.rmsnorm_bwd(d_xn, x_in, fz[o + "ln1"], rstd1, dres=d_h1)
             saved[l] = None
+            # nothing of this layer but dx stays bound while the next one is recomputed
+            del x_in, rstd1, qkv, att, lse, h1, rstd2, gu, d_hn, d_h1, d_att, dqkv, q4, k4, v4, dq4, dk4, dv4, d_xn
         if train_llm:                                           # embed_tokens.weight.grad: scatter-add of the text rows
             ops.scatter_add_rows_(ps.g("model.embed_tokens.weight"), dx, plan["embed_idx"])
         return dx

@@ -301,6 +301,36 @@ class EngineModule(nn.Module):
     def get_model(self):
         return self.model
 
+    # ---- gradient checkpointing, as transformers.Trainer / the reference's entry points drive it (trainer.py `gradient_checkpointing_enable`,
+    # ola_vlm_train.py:1049-1055, train.py:975-977, every scripts/train/*.sh: `--gradient_checkpointing True`)
+    supports_gradient_checkpointing = True
+
+    def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
+        """The decoder backward recomputes each layer from its input (Engine.gradient_checkpointing; bit-identical gradients).  Selects "full"
+        unless config.gradient_checkpointing already names a mode ("full" / "keep_attn").  HF's kwargs (`use_reentrant`, ...) describe
+        torch.utils.checkpoint, which is not involved: accepted and ignored."""
+        from ..engine import CKPT_MODES
+        if getattr(self.config, "gradient_checkpointing", False) not in CKPT_MODES:
+            self.config.gradient_checkpointing = "full"
+        if self._engine is not None:
+            self._engine.gradient_checkpointing = self.config.gradient_checkpointing
+
+    def gradient_checkpointing_disable(self):
+        self.config.gradient_checkpointing = False
+        if self._engine is not None:
+            self._engine.gradient_checkpointing = False
+
+    @property
+    def is_gradient_checkpointing(self):
+        return bool(getattr(self.config, "gradient_checkpointing", False))
+
+    def enable_input_require_grads(self):
+        """No-op.  HF registers a hook that makes the embedding output require grad so that checkpointed segments of a frozen LLM get a
+        gradient path (ola_vlm_train.py:1049-1051); the engine computes d inputs_embeds whether or not autograd asks for it."""
+
+    def get_input_embeddings(self):
+        return self.model.embed_tokens
+
     def state_dict(self, *args, **kwargs):
         """nn.Module.state_dict after folding in in-place edits of the Parameters (see _sync_trainable)."""
         if self._engine is not None:
