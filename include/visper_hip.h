@@ -243,7 +243,11 @@ int vp_add_i32(long n, int* x, int delta, vp_stream_t stream);
 
 /* ---- losses.  NTP CE (ola_llama.py:121-136: logits.float(), shifted CrossEntropyLoss, ignore -100);
  * embedding distillation (base_ola_vlm.py:289-320 _emb_loss; ola_utils.py:108-125
- * calculate_contrastive_loss; :96-106 dist_collect -> tgt_all is the rank-ordered all-gather). */
+ * calculate_contrastive_loss; :96-106 dist_collect -> tgt_all is the rank-ordered all-gather).
+ * vp_ce_fwd_bwd: logits [rows, V] bf16 with row stride ld (ld % 8 == 0, ld >= V; columns V .. ld-1 are neither read nor written), overwritten
+ *   in place with (softmax - onehot) * grad_scale when write_grad != 0 (left untouched when 0); row_loss[r] = logsumexp - logit[label], 0 for an
+ *   ignored row (its gradient row is zeroed).  PRECONDITION: every label is negative (ignored; the reference uses -100) or in [0, V): the kernel
+ *   reads logits[r, label] unchecked, so a label >= V is an out-of-bounds read. */
 int vp_ce_fwd_bwd(long rows, int V, void* logits, long ld, const long* labels, float* row_loss, float grad_scale,
                   int write_grad, vp_stream_t stream);
 /* vp_emb_loss_fwd: ONE launch (streaming MFMA/dot2 pass + deterministic last-block tree + the B x Bw softmax); out3 = {emb_loss, sl1,

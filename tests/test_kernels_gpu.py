@@ -957,14 +957,15 @@ def test_attention_d96_fused_qkv_views_fwd_bwd(ops, S, window, kvl):
     close(dv, vr.grad, rtol=3e-2, what="attn d96 dv")
 
 
-@pytest.mark.parametrize("causal", [True, False])
-def test_attention_d128_rescale_branch_mid_sequence(ops, causal):
-    """The deferred running max of the D = 128 forward kernels (O / l are only rescaled when a tile's max exceeds the running max by > 2^8):
+@pytest.mark.parametrize("causal,D", [pytest.param(True, 128, id="True"), pytest.param(False, 128, id="False"),
+                                      pytest.param(True, 96, id="True-96"), pytest.param(False, 96, id="False-96")])
+def test_attention_d128_rescale_branch_mid_sequence(ops, causal, D):
+    """The deferred running max of the D = 128 forward kernels (and, with 3 of 4 k-steps, D = 96; O / l are only rescaled when a tile's max exceeds the running max by > 2^8):
     on random inputs that branch fires in the first tile only, so a stale or half-applied rescale later in the sequence would go unnoticed.
     Here a few keys are aligned with a few query rows so that their scores jump by ~30 and then by another ~16 log2 units in LATER tiles
     (key positions in both key blocks of a 64-key tile and in both lane halves of the 32x32 layout; query rows in different waves), the rest
     of the rows stay ordinary.  Forward vs fp32 softmax over the whole tensor, backward (which consumes the forward's lse) vs autograd."""
-    B, Hq, Hkv, S, D = 1, 4, 2, 512, 128
+    B, Hq, Hkv, S = 1, 4, 2, 512
     q, k, v, do = rnd(B, S, Hq, D, seed=301), rnd(B, S, Hkv, D, seed=302), rnd(B, S, Hkv, D, seed=303), rnd(B, S, Hq, D, seed=304)
     u = torch.ones(D) / math.sqrt(D)
     for j, mag in ((130, 16.0), (140, 16.0), (170, 16.0), (300, 24.0), (450, 32.0)):
