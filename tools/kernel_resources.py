@@ -64,7 +64,45 @@ def kernels(path):
     return res
 
 
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+
+
+def disasm_hashes(path):
+    """{kernel symbol: sha256 of its disassembly}: what a host-side refactor must leave alone.  Compared per symbol, since the order of the
+    kernels in the code object (and so the blob) moves with the order of their instantiation in the host code."""
+    import hashlib
+    res = {}
+    for triple, blob in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(blob)
+            f.flush()
+            txt = subprocess.run([OBJDUMP, "-d", "--no-leading-addr", "--no-show-raw-insn", f.name], capture_output=True, text=True, check=True).stdout
+        for m in re.finditer(r"^<(\S+)>:\n(.*?)(?=^<|\Z)", txt, flags=re.M | re.S):
+            # what moves with a kernel's place in the code object and is no change of the kernel: the printer's own address column (the encoding
+            # words after it stay), the pc-relative distance to a __device__ global (the literal of the s_add_u32 after s_getpc_b64), and the
+            # zero fill after the section's last kernel
+            body = re.sub(r"// [0-9A-F]{8,}: ", "// ", m.group(2))
+            body = re.sub(r"(s_getpc_b64 [^\n]*\n\s*s_add_u32 s\d+, s\d+, )0x[0-9a-f]+\s*// ([0-9A-F]{8}) [0-9A-F]{8}", r"\1PCREL // \2", body)
+            body = re.sub(r"(\s*\.\.\.)?\s*\Z", "", body)
+            res[m.group(1)] = hashlib.sha256(body.encode()).hexdigest()
+    return res
+
+
+def compare(a, b):
+    """python tools/kernel_resources.py --compare old.so new.so: same kernel names, same disassembly per name, same metadata table"""
+    ha, hb = disasm_hashes(a), disasm_hashes(b)
+    differ = sorted(n for n in set(ha) & set(hb) if ha[n] != hb[n])
+    same_meta = kernels(a) == kernels(b)
+    print(f"{len(ha)} / {len(hb)} kernel symbols, {len(set(ha) ^ set(hb))} names on one side only, {len(differ)} disassemblies differ, "
+          f"metadata {'equal' if same_meta else 'DIFFERS'}")
+    for n in sorted(set(ha) ^ set(hb)) + differ:
+        print("  ", n)
+    return 0 if set(ha) == set(hb) and not differ and same_meta else 1
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
     so = sys.argv[1] if len(sys.argv) > 1 and os.path.exists(sys.argv[1]) else os.path.join(os.path.dirname(__file__), "..", "visper-lm_amd", "libvisper_hip.so")
     flt = sys.argv[2] if len(sys.argv) > 2 else (sys.argv[1] if len(sys.argv) > 1 and not os.path.exists(sys.argv[1]) else "")
     for name, d in sorted(kernels(so).items()):

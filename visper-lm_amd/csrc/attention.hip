@@ -473,66 +473,35 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
 template <int D>
 static constexpr int kv_lds_bytes() { return 4 * 64 * (D + 16) * 2; }     // K,V tiles x 2 buffers
 
-static int vp_attn_order() {                           // VP_ATTN_ORDER=0|1 (see AttnParams::order)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("VP_ATTN_ORDER"); v = e ? atoi(e) : 0; }
-  return v;
-}
-
-static bool vp_fwdm_enabled() {                        // the 32x32x16 swapped-product forward (D = 128) is the default since round 3; VP_ATTN_FWDM=0: the 16-row kernel
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("VP_ATTN_FWDM"); v = e ? atoi(e) : 1; }
-  return v != 0;
-}
+static int vp_attn_order() { static const int v = vp_env_int("VP_ATTN_ORDER", 0); return v; }      // VP_ATTN_ORDER=0|1 (see AttnParams::order)
+// the 32x32x16 swapped-product forward (D = 128) is the default since round 3; VP_ATTN_FWDM=0: the 16-row kernel
+static int vp_attn_fwdm() { static const int v = vp_env_int("VP_ATTN_FWDM", 1); return v; }
+// VP_ATTN_BWD64: 1 (default) = the one-wave-per-SIMD backward kernels of round 5 (attention_bwd64.h); 2 = round 5's dK/dV kernel behind round 4's
+// dQ kernel (which then writes the statistics planes); 0 = round 4's kernels
+static int vp_bwd64_mode() { static const int v = vp_env_int("VP_ATTN_BWD64", 1); return v; }
 
 template <int D>
 static int launch_fwd(const AttnParams& p_in, int causal, hipStream_t s) {
   AttnParams p = p_in;
   p.order = (p.B <= 65535 && (p.Sq + 127) / 128 <= 65535) ? vp_attn_order() : 0;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-    attr = true;
-  }
-  const dim3 grid = p.order ? dim3(p.Hq, (p.Sq + 127) / 128, p.B) : dim3(p.Hq, p.B, (p.Sq + 127) / 128);
+  constexpr unsigned LDS = kv_lds_bytes<D>();
+  const dim3 grid = p.order ? dim3(p.Hq, (p.Sq + 127) / 128, p.B) : dim3(p.Hq, p.B, (p.Sq + 127) / 128), blk(512);
+  const bool bias = p.bias_h || p.bias_b;
   if constexpr (D == 128 || D == 96) {
-    if (!p.bias_h && !p.bias_b && vp_fwdm_enabled()) {                  // 32x32x16 swapped-product kernel, 256-row blocks (attention_d128.h)
-      static bool attrm = false;
-      if (!attrm) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd128m_kernel<true, D>, hipFuncAttributeMaxDynamicSharedMemorySize, FWDM_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_fwd128m_kernel<false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, FWDM_LDS);
-        attrm = true;
-      }
+    if (!bias && vp_attn_fwdm() != 0) {                                 // 32x32x16 swapped-product kernel, 256-row blocks (attention_d128.h)
       const int nb = (p.Sq + 255) / 256;
       const dim3 gm = p.order ? dim3(p.Hq, nb, p.B) : dim3(p.Hq, p.B, nb);
-      if (causal) hipLaunchKernelGGL((attn_fwd128m_kernel<true, D>), gm, dim3(512), FWDM_LDS, s, p);
-      else hipLaunchKernelGGL((attn_fwd128m_kernel<false, D>), gm, dim3(512), FWDM_LDS, s, p);
+      if (causal) vp_launch<attn_fwd128m_kernel<true, D>>(gm, blk, FWDM_LDS, s, p);
+      else vp_launch<attn_fwd128m_kernel<false, D>>(gm, blk, FWDM_LDS, s, p);
       return vp_check_launch("vp_attn_fwd");
     }
   }
-  if (D == 128 && causal && !p.bias_h && !p.bias_b && getenv("VP_ATTN_DBG")) {       // dev aid: phase stamps
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-    hipLaunchKernelGGL((attn_fwd_kernel<D, true, false, true>), grid, dim3(512), kv_lds_bytes<D>(), s, p);
-    return vp_check_launch("vp_attn_fwd");
-  }
-  if (p.bias_h || p.bias_b) {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<D, true, true>), grid, dim3(512), kv_lds_bytes<D>(), s, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<D, false, true>), grid, dim3(512), kv_lds_bytes<D>(), s, p);
-  } else {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), grid, dim3(512), kv_lds_bytes<D>(), s, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), grid, dim3(512), kv_lds_bytes<D>(), s, p);
-  }
+  if (D == 128 && causal && !bias && getenv("VP_ATTN_DBG")) vp_launch<attn_fwd_kernel<D, true, false, true>>(grid, blk, LDS, s, p);   // dev aid: phase stamps
+  else if (bias && causal) vp_launch<attn_fwd_kernel<D, true, true>>(grid, blk, LDS, s, p);
+  else if (bias) vp_launch<attn_fwd_kernel<D, false, true>>(grid, blk, LDS, s, p);
+  else if (causal) vp_launch<attn_fwd_kernel<D, true>>(grid, blk, LDS, s, p);
+  else vp_launch<attn_fwd_kernel<D, false>>(grid, blk, LDS, s, p);
   return vp_check_launch("vp_attn_fwd");
-}
-// VP_ATTN_BWD64: 1 (default) = the one-wave-per-SIMD backward kernels of round 5 (attention_bwd64.h); 2 = round 5's dK/dV kernel behind round 4's
-// dQ kernel (which then writes the statistics planes); 0 = round 4's kernels
-static int vp_bwd64_mode() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("VP_ATTN_BWD64"); v = e ? atoi(e) : 1; }
-  return v;
 }
 
 template <int D>
@@ -542,82 +511,45 @@ static int launch_bwd(const AttnParams& p_in, int causal, hipStream_t s) {
   const dim3 g1 = p.order ? dim3(p.Hkv, (p.Skv + 127) / 128, p.B) : dim3(p.Hkv, p.B, (p.Skv + 127) / 128);
   const dim3 g2 = p.order ? dim3(p.Hq, (p.Sq + 127) / 128, p.B) : dim3(p.Hq, p.B, (p.Sq + 127) / 128);
   if constexpr (D == 128 || D == 96) {
+    // fused RoPE backward: its own instantiations (training: causal only)
+    if (p.rope_cos && !causal) { vp_set_error("vp_attn_bwd_rope: causal attention only"); return VP_ERR_UNSUPPORTED_SHAPE; }
+    // both kernel pairs: one instantiation per (causal, rope) case, dQ first
+    auto by_case = [&](auto&& run) {
+      if (p.rope_cos) run(std::true_type{}, std::true_type{});
+      else if (causal) run(std::true_type{}, std::false_type{});
+      else run(std::false_type{}, std::false_type{});
+      return vp_check_launch("vp_attn_bwd");
+    };
     if (vp_bwd64_mode() != 0) {                         // round 5: one wave per SIMD, 64 rows per wave, 32x32x16 MFMAs (attention_bwd64.h)
-      if (p.rope_cos && !causal) { vp_set_error("vp_attn_bwd_rope: causal attention only"); return VP_ERR_UNSUPPORTED_SHAPE; }
       const int nkb = (p.Skv + 255) / 256, nqb = (p.Sq + 255) / 256;
       const dim3 h1 = p.order ? dim3(p.Hkv, nkb, p.B) : dim3(p.Hkv, p.B, nkb);
       const dim3 h2 = p.order ? dim3(p.Hq, nqb, p.B) : dim3(p.Hq, p.B, nqb);
       const bool old_dq = vp_bwd64_mode() == 2;
       if (old_dq) p.stat_planes = 1;
-      static bool attr_o = false;
-      if (old_dq && !attr_o) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<true, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<false, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<true, true, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-        attr_o = true;
-      }
-#define VP_B64_LAUNCH(C_, R_)                                                                                                        \
-  {                                                                                                                                  \
-    static bool a_ = false;                                                                                                          \
-    if (!a_) {                                                                                                                       \
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq64w_kernel<C_, R_, D>, hipFuncAttributeMaxDynamicSharedMemorySize, B64_DQ_LDS);   \
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv64w_kernel<C_, R_, D>, hipFuncAttributeMaxDynamicSharedMemorySize, B64_KV_LDS); \
-      a_ = true;                                                                                                                     \
-    }                                                                                                                                \
-    if (old_dq) hipLaunchKernelGGL((attn_bwd_dq128_kernel<C_, R_, D>), g2, dim3(256), DQ128_LDS, s, p);                              \
-    else hipLaunchKernelGGL((attn_bwd_dq64w_kernel<C_, R_, D>), h2, dim3(256), B64_DQ_LDS, s, p);     /* first: writes the statistics planes */ \
-    hipLaunchKernelGGL((attn_bwd_dkdv64w_kernel<C_, R_, D>), h1, dim3(256), B64_KV_LDS, s, p);                                       \
-  }
-      if (p.rope_cos) VP_B64_LAUNCH(true, true)
-      else if (causal) VP_B64_LAUNCH(true, false)
-      else VP_B64_LAUNCH(false, false)
-#undef VP_B64_LAUNCH
-      return vp_check_launch("vp_attn_bwd");
+      return by_case([&](auto C, auto R) {
+        if (old_dq) vp_launch<attn_bwd_dq128_kernel<C(), R(), D>>(g2, dim3(256), DQ128_LDS, s, p);
+        else vp_launch<attn_bwd_dq64w_kernel<C(), R(), D>>(h2, dim3(256), B64_DQ_LDS, s, p);          // first: writes the statistics planes
+        vp_launch<attn_bwd_dkdv64w_kernel<C(), R(), D>>(h1, dim3(256), B64_KV_LDS, s, p);
+      });
     }
     // the LDS-DMA ring kernels (attention_d128.h): dQ first — it also writes the (lse, delta) pairs the dK/dV kernel streams
-    static bool attr2 = false;
-    if (!attr2) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv128_kernel<true, DKDV_KT, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DKDV128_LDS);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv128_kernel<false, DKDV_KT, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DKDV128_LDS);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<true, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<false, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-      attr2 = true;
-    }
-    if (p.rope_cos) {                                   // fused RoPE backward: its own instantiations (training: causal only)
-      if (!causal) { vp_set_error("vp_attn_bwd_rope: causal attention only"); return VP_ERR_UNSUPPORTED_SHAPE; }
-      static bool attr3 = false;
-      if (!attr3) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv128_kernel<true, DKDV_KT, true, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DKDV128_LDS);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_dq128_kernel<true, true, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ128_LDS);
-        attr3 = true;
-      }
-      hipLaunchKernelGGL((attn_bwd_dq128_kernel<true, true, D>), g2, dim3(256), DQ128_LDS, s, p);
-      hipLaunchKernelGGL((attn_bwd_dkdv128_kernel<true, DKDV_KT, true, D>), g1, dim3(64 * (8 / DKDV_KT)), DKDV128_LDS, s, p);
-    } else if (causal) {
-      hipLaunchKernelGGL((attn_bwd_dq128_kernel<true, false, D>), g2, dim3(256), DQ128_LDS, s, p);
-      hipLaunchKernelGGL((attn_bwd_dkdv128_kernel<true, DKDV_KT, false, D>), g1, dim3(64 * (8 / DKDV_KT)), DKDV128_LDS, s, p);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dq128_kernel<false, false, D>), g2, dim3(256), DQ128_LDS, s, p);
-      hipLaunchKernelGGL((attn_bwd_dkdv128_kernel<false, DKDV_KT, false, D>), g1, dim3(64 * (8 / DKDV_KT)), DKDV128_LDS, s, p);
-    }
+    return by_case([&](auto C, auto R) {
+      vp_launch<attn_bwd_dq128_kernel<C(), R(), D>>(g2, dim3(256), DQ128_LDS, s, p);
+      vp_launch<attn_bwd_dkdv128_kernel<C(), DKDV_KT, R(), D>>(g1, dim3(64 * (8 / DKDV_KT)), DKDV128_LDS, s, p);
+    });
   } else {
     const long rows = (long)p.B * p.Hq * p.Sq;
-    hipLaunchKernelGGL((attn_delta_kernel<D>), dim3((unsigned)min(8192L, (rows + 15) / 16)), dim3(256), 0, s, p);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kv_lds_bytes<D>());
-      attr = true;
-    }
+    constexpr unsigned LDS = kv_lds_bytes<D>();
+    vp_launch<attn_delta_kernel<D>>(dim3((unsigned)min(8192L, (rows + 15) / 16)), dim3(256), 0, s, p);
     if (causal) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, true>), g1, dim3(512), 0, s, p);
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<D, true>), g2, dim3(512), kv_lds_bytes<D>(), s, p);
+      vp_launch<attn_bwd_dkdv_kernel<D, true>>(g1, dim3(512), 0, s, p);
+      vp_launch<attn_bwd_dq_kernel<D, true>>(g2, dim3(512), LDS, s, p);
     } else {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, false>), g1, dim3(512), 0, s, p);
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false>), g2, dim3(512), kv_lds_bytes<D>(), s, p);
+      vp_launch<attn_bwd_dkdv_kernel<D, false>>(g1, dim3(512), 0, s, p);
+      vp_launch<attn_bwd_dq_kernel<D, false>>(g2, dim3(512), LDS, s, p);
     }
+    return vp_check_launch("vp_attn_bwd");
   }
-  return vp_check_launch("vp_attn_bwd");
 }
 
 static int check_attn(const char* w, int B, int Hq, int Hkv, int Sq, int Skv, int D) {
@@ -625,6 +557,33 @@ static int check_attn(const char* w, int B, int Hq, int Hkv, int Sq, int Skv, in
   VP_REQUIRE(Hq % Hkv == 0, VP_ERR_BAD_ARG, "%s: Hq %% Hkv != 0", w);
   VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d not in {32,64,96,128}", w, D);
   return VP_OK;
+}
+
+// f(std::integral_constant<int, D>) for the run-time head_dim (one of check_attn's four)
+template <class F>
+static int for_head_dim(int D, F&& f) {
+  switch (D) {
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 96: return f(std::integral_constant<int, 96>{});
+    default: return f(std::integral_constant<int, 128>{});
+  }
+}
+
+// what the four entry points share; the backward ones add the gradients with attn_grads
+static AttnParams attn_params(int B, int Hq, int Hkv, int Sq, int Skv, const void* q, long q_bs, long q_ts, const void* k, long k_bs, long k_ts,
+                              const void* v, long v_bs, long v_ts, const void* o, long o_bs, long o_ts, const float* lse, const int* kv_len,
+                              int window, float scale) {
+  AttnParams p{};
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = (float*)lse;
+  p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Skv = Skv; p.window = window; p.kv_len = kv_len; p.scale = scale;
+  return p;
+}
+static void attn_grads(AttnParams& p, const void* dout, long do_bs, long do_ts, void* dq, long dq_bs, long dq_ts, void* dk, long dk_bs, long dk_ts,
+                       void* dv, long dv_bs, long dv_ts, float* delta) {
+  p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.delta = delta;
+  p.do_bs = do_bs; p.do_ts = do_ts; p.dq_bs = dq_bs; p.dq_ts = dq_ts; p.dk_bs = dk_bs; p.dk_ts = dk_ts; p.dv_bs = dv_bs; p.dv_ts = dv_ts;
 }
 
 extern "C" {
@@ -637,16 +596,8 @@ int vp_attn_fwd(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void* q, l
                 int causal, int window, float scale, hipStream_t s) {
   int e = check_attn("vp_attn_fwd", B, Hq, Hkv, Sq, Skv, D);
   if (e) return e;
-  AttnParams p{};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Skv = Skv; p.window = window; p.kv_len = kv_len; p.scale = scale;
-  switch (D) {
-    case 32: return launch_fwd<32>(p, causal, s);
-    case 64: return launch_fwd<64>(p, causal, s);
-    case 96: return launch_fwd<96>(p, causal, s);
-    default: return launch_fwd<128>(p, causal, s);
-  }
+  const AttnParams p = attn_params(B, Hq, Hkv, Sq, Skv, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse, kv_len, window, scale);
+  return for_head_dim(D, [&](auto d) { return launch_fwd<d()>(p, causal, s); });
 }
 
 // dev aid: the forward kernel's phase stamps of the last VP_ATTN_DBG launch (16 longs: waves 0 and 7 of block (0,0,0))
@@ -662,18 +613,10 @@ int vp_attn_fwd_bias(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void*
                      hipStream_t s) {
   int e = check_attn("vp_attn_fwd_bias", B, Hq, Hkv, Sq, Skv, D);
   if (e) return e;
-  AttnParams p{};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Skv = Skv; p.window = window; p.kv_len = kv_len; p.scale = scale;
+  AttnParams p = attn_params(B, Hq, Hkv, Sq, Skv, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse, kv_len, window, scale);
   VP_REQUIRE(!bias_b || bias_nb > 0, VP_ERR_BAD_ARG, "vp_attn_fwd_bias: bias_nb");
   p.bias_h = bias_h; p.bias_b = bias_b; p.bias_nb = bias_nb;
-  switch (D) {
-    case 32: return launch_fwd<32>(p, causal, s);
-    case 64: return launch_fwd<64>(p, causal, s);
-    case 96: return launch_fwd<96>(p, causal, s);
-    default: return launch_fwd<128>(p, causal, s);
-  }
+  return for_head_dim(D, [&](auto d) { return launch_fwd<d()>(p, causal, s); });
 }
 
 // delta: fp32 workspace of 3 * B * Hq * Sq floats (delta, then interleaved (lse, delta) pairs).  dq/dk/dv use the same [B,S,H,D] addressing with their own strides.
@@ -685,18 +628,9 @@ int vp_attn_bwd(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void* q, l
   int e = check_attn("vp_attn_bwd", B, Hq, Hkv, Sq, Skv, D);
   if (e) return e;
   VP_REQUIRE(lse && delta && dout && dq && dk && dv, VP_ERR_BAD_ARG, "vp_attn_bwd: null pointer");
-  AttnParams p{};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = (float*)lse;
-  p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.delta = delta;
-  p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
-  p.do_bs = do_bs; p.do_ts = do_ts; p.dq_bs = dq_bs; p.dq_ts = dq_ts; p.dk_bs = dk_bs; p.dk_ts = dk_ts; p.dv_bs = dv_bs; p.dv_ts = dv_ts;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Skv = Skv; p.window = window; p.kv_len = kv_len; p.scale = scale;
-  switch (D) {
-    case 32: return launch_bwd<32>(p, causal, s);
-    case 64: return launch_bwd<64>(p, causal, s);
-    case 96: return launch_bwd<96>(p, causal, s);
-    default: return launch_bwd<128>(p, causal, s);
-  }
+  AttnParams p = attn_params(B, Hq, Hkv, Sq, Skv, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse, kv_len, window, scale);
+  attn_grads(p, dout, do_bs, do_ts, dq, dq_bs, dq_ts, dk, dk_bs, dk_ts, dv, dv_bs, dv_ts, delta);
+  return for_head_dim(D, [&](auto d) { return launch_bwd<d()>(p, causal, s); });
 }
 
 // vp_attn_bwd with the RoPE backward of dq / dk fused into the stores (reference: HF LlamaAttention.forward applies apply_rotary_pos_emb
@@ -713,12 +647,8 @@ int vp_attn_bwd_rope(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void*
   VP_REQUIRE(lse && delta && dout && dq && dk && dv && rope_cos && rope_sin, VP_ERR_BAD_ARG, "vp_attn_bwd_rope: null pointer");
   VP_REQUIRE((D == 128 || D == 96) && causal, VP_ERR_UNSUPPORTED_SHAPE, "vp_attn_bwd_rope: head_dim 128 or 96, causal only (got %d, causal %d)", D, causal);
   VP_REQUIRE(((((uintptr_t)rope_cos) | ((uintptr_t)rope_sin)) & 15) == 0, VP_ERR_BAD_ARG, "vp_attn_bwd_rope: tables must be 16-byte aligned");
-  AttnParams p{};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = (float*)lse;
-  p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.delta = delta;
-  p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
-  p.do_bs = do_bs; p.do_ts = do_ts; p.dq_bs = dq_bs; p.dq_ts = dq_ts; p.dk_bs = dk_bs; p.dk_ts = dk_ts; p.dv_bs = dv_bs; p.dv_ts = dv_ts;
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Skv = Skv; p.window = window; p.kv_len = kv_len; p.scale = scale;
+  AttnParams p = attn_params(B, Hq, Hkv, Sq, Skv, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse, kv_len, window, scale);
+  attn_grads(p, dout, do_bs, do_ts, dq, dq_bs, dq_ts, dk, dk_bs, dk_ts, dv, dv_bs, dv_ts, delta);
   p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_pos = rope_pos;
   return D == 128 ? launch_bwd<128>(p, causal, s) : launch_bwd<96>(p, causal, s);
 }

@@ -28,6 +28,22 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 void vp_set_error(const char* fmt, ...);
 int vp_check_launch(const char* what);
 
+// Run-time switch VP_*: atoi of the environment variable, `dflt` when it is unset.  Every switch is read once per process, into a
+// `static const int` at its point of use (so a test of a switch's variants runs each in a child process); DESIGN.md section 4 lists them all.
+__attribute__((visibility("hidden"))) int vp_env_int(const char* name, int dflt);
+
+// The one way a kernel with dynamic LDS is launched: the first launch of each instantiation K raises its dynamic-LDS limit to `lds` (needed above
+// 64 KB; a function-local static, so once per process and thread-safe), every launch then goes out with `lds` bytes.  Each kernel has one LDS
+// size, a compile-time constant of its file.  lds == 0 (static LDS only) sets no attribute.
+template <auto K, class... P>
+static void vp_launch(dim3 grid, dim3 block, unsigned lds, hipStream_t s, const P&... p) {
+  if (lds) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)once;
+  }
+  hipLaunchKernelGGL(K, grid, block, lds, s, p...);
+}
+
 #define VP_REQUIRE(cond, code, ...)            \
   do {                                         \
     if (!(cond)) {                             \

@@ -599,8 +599,8 @@ ElPlan el_plan(int B, int Bw, long D) {
   const long ks = 32L * nv * (p.pack ? 2 : 1);
   const long nsteps = (D + ks - 1) / ks;
   // >= spw k-steps per wave, at most `cap` streaming blocks per chunk and MAX_GROUPS first-level groups in total
-  static const long cap = getenv("VP_EL_NBLK") ? atol(getenv("VP_EL_NBLK")) : 256L;       // dev knob (tools/emb_loss_bench.py)
-  static const long spw = getenv("VP_EL_SPW") ? atol(getenv("VP_EL_SPW")) : 2L;             // target k-steps per wave
+  static const long cap = vp_env_int("VP_EL_NBLK", 256);                                   // dev knob (tools/emb_loss_bench.py)
+  static const long spw = vp_env_int("VP_EL_SPW", 2);                                      // target k-steps per wave
   long nblk = max(1L, min(min(cap, (long)G1 * G1), (nsteps + 4 * spw - 1) / (4 * spw)));
   while (p.njc * ((nblk + G1 - 1) / G1) > MAX_GROUPS) nblk /= 2;
   p.nblk = (int)nblk;

@@ -2,7 +2,7 @@
 // Both operands are K-contiguous ("NT"): activations [tokens, features] x nn.Linear weights [out, in].
 // (dgrad uses the pre-transposed frozen weight, wgrad uses explicitly transposed operands — DESIGN.md.)
 //
-// Kernels (dispatch in vp_gemm_bf16):
+// Kernels (which one a call runs: gemm_route.h; how it is launched: gemm_launch below):
 //   gemm_nt_256p8   the production kernel for every large problem: persistent 256x256x64 tiles, 8 waves, 8-phase ping-pong
 //                   (see the comment on the kernel), fused bias / activation / residual / SwiGLU epilogues
 //   gemm_nt_256     the plain persistent 256-tile kernel it grew out of (one barrier per K-tile); kept as the A/B reference
@@ -14,6 +14,7 @@
 // ends up with 4 consecutive output columns of one token row.  Block ids are remapped XCD-aware so tiles sharing an operand
 // panel sit in one XCD's L2.
 #include "common.h"
+#include "gemm_route.h"
 #include <cstdlib>
 #include <utility>
 #include <type_traits>
@@ -27,8 +28,6 @@ constexpr int vp_w4_rd_slot(int g) {
 }
 // byte offset of B fragment r = 4 h + 2 s + jj from the lane's base row: rows 64 h + 32 s + 4 jj of 128 bytes
 constexpr int vp_w4_boff(int r) { return ((r >> 2) * 64 + ((r >> 1) & 1) * 32 + (r & 1) * 4) * 128; }
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_QUICK_GELU = 2, EPI_RELU = 3 };
 
 struct GemmArgs {
   const bf16_t* A;
@@ -1939,19 +1938,40 @@ __global__ void occupy_kernel(long cycles) {
   if (occ_lds[threadIdx.x] == 77) occ_lds[0] = 2;
 }
 
-static bool vp_c_nt_enabled() {                        // VP_GEMM_C_NT=0 switches the non-temporal C stores off (A/B)
-  static int e = -1;
-  if (e < 0) { const char* v = getenv("VP_GEMM_C_NT"); e = v ? atoi(v) : 1; }
-  return e != 0;
+static int vp_w4_switch() { static const int v = vp_env_int("VP_GEMM_W4", 1); return v; }          // see gemm_w4_wanted (gemm_route.h)
+static int vp_ph4_switch() { static const int v = vp_env_int("VP_GEMM_PH4", 1); return v; }        // see gemm_route: 0 selects the 8-phase loop
+static int vp_c_nt_switch() { static const int v = vp_env_int("VP_GEMM_C_NT", 1); return v; }      // 0 switches the non-temporal C stores off (A/B)
+
+#ifdef VP_DEBUG
+static int g_gemm_dbg = -1;                           // VP_GEMM_DBG, or vp_debug_gemm_flags(): measurement flags exist in -DVP_DEBUG builds only
+static int vp_gemm_dbg() {
+  if (g_gemm_dbg < 0) g_gemm_dbg = vp_env_int("VP_GEMM_DBG", 0);
+  return g_gemm_dbg;
+}
+#else
+static constexpr int vp_gemm_dbg() { return 0; }      // the sealed library reads no debug switch (a stray VP_GEMM_DBG cannot reach a kernel)
+#endif
+
+// The launch table: kernel id of gemm_route.h -> instantiation, block size, dynamic LDS (0: static LDS only)
+static constexpr unsigned W4_LDS = 163840, P8_LDS = 131072;
+static int gemm_launch(const char* what, int kernel, bool f32, unsigned grid, hipStream_t s, const GemmArgs& p) {
+  const dim3 g(grid), b4(256), b8(512);
+  switch (kernel) {
+    case GK_W4: f32 ? vp_launch<gemm_nt_256w4<true>>(g, b4, W4_LDS, s, p) : vp_launch<gemm_nt_256w4<false>>(g, b4, W4_LDS, s, p); break;
+    case GK_W4G: vp_launch<gemm_nt_256w4<false, 1>>(g, b4, W4_LDS, s, p); break;
+    case GK_W4F: vp_launch<gemm_nt_256w4<false, 2>>(g, b4, W4_LDS, s, p); break;
+    case GK_P8: f32 ? vp_launch<gemm_nt_256p8<true>>(g, b8, P8_LDS, s, p) : vp_launch<gemm_nt_256p8<false>>(g, b8, P8_LDS, s, p); break;
+    case GK_PH4: vp_launch<gemm_nt_256p8<false, true>>(g, b8, P8_LDS, s, p); break;
+    case GK_NT256: f32 ? vp_launch<gemm_nt_256<true>>(g, b8, P8_LDS, s, p) : vp_launch<gemm_nt_256<false>>(g, b8, P8_LDS, s, p); break;
+    case GK_NT128: f32 ? vp_launch<gemm_nt_128<true>>(g, b4, 0, s, p) : vp_launch<gemm_nt_128<false>>(g, b4, 0, s, p); break;
+    case GK_GENERIC: f32 ? vp_launch<gemm_nt_generic<true>>(g, b4, 0, s, p) : vp_launch<gemm_nt_generic<false>>(g, b4, 0, s, p); break;
+    case GK_TN: f32 ? vp_launch<gemm_tn_256p8<true>>(g, b8, P8_LDS, s, p) : vp_launch<gemm_tn_256p8<false>>(g, b8, P8_LDS, s, p); break;
+    default: vp_set_error("%s: no kernel %d", what, kernel); return VP_ERR_BAD_ARG;
+  }
+  return vp_check_launch(what);
 }
 
-static bool vp_ph4_enabled() {
-  static int e = -1;
-  // default ON since round 2: in-step A/B on one box, alternating runs: 458.1 / 459.0 ms per step against 461.7 / 462.5 with the 8-phase loop
-  // (GEMM 1337 vs 1324 TFLOP/s), bit-identical results; VP_GEMM_PH4=0 selects the 8-phase loop
-  if (e < 0) { const char* v = getenv("VP_GEMM_PH4"); e = v ? atoi(v) : 1; }
-  return e != 0;
-}
+static unsigned al16(const void* p) { return (unsigned)(((uintptr_t)p) & 15); }
 
 extern "C" {
 
@@ -1962,23 +1982,10 @@ long vp_gemm_sched_workspace_bytes(void) { return 64; }
 // for `cycles` shader cycles -- a stand-in for a collective kernel holding CUs
 int vp_debug_occupy(int blocks, long cycles, hipStream_t stream) {
   VP_REQUIRE(blocks > 0 && cycles > 0, VP_ERR_BAD_ARG, "vp_debug_occupy: bad args");
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)occupy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr = true; }
-  hipLaunchKernelGGL(occupy_kernel, dim3(blocks), dim3(64), 65536, stream, cycles);
+  vp_launch<occupy_kernel>(dim3(blocks), dim3(64), 65536, stream, cycles);
   return vp_check_launch("vp_debug_occupy");
 }
-#endif
 
-#ifdef VP_DEBUG
-static int g_gemm_dbg = -1;                           // VP_GEMM_DBG, or vp_debug_gemm_flags(): measurement flags exist in -DVP_DEBUG builds only
-static int vp_gemm_dbg() {
-  if (g_gemm_dbg < 0) { const char* e = getenv("VP_GEMM_DBG"); g_gemm_dbg = e ? atoi(e) : 0; }
-  return g_gemm_dbg;
-}
-#else
-static constexpr int vp_gemm_dbg() { return 0; }      // the sealed library reads no debug switch (a stray VP_GEMM_DBG cannot reach a kernel)
-#endif
-#ifdef VP_DEBUG
 // measurement aid (bench.py: shader clock under load): 0x10000 = the persistent kernel's first tile writes wall-clock / shader-cycle stamps
 int vp_debug_gemm_flags(int flags) { g_gemm_dbg = flags; return 0; }
 
@@ -1994,107 +2001,17 @@ int vp_gemm_bf16(int M, int N, int K, const void* A, long lda, const void* B, lo
   VP_REQUIRE(A && B && C, VP_ERR_BAD_ARG, "vp_gemm_bf16: null operand");
   VP_REQUIRE(lda >= K && ldb >= K && ldc >= N, VP_ERR_BAD_ARG, "vp_gemm_bf16: leading dims too small");
   VP_REQUIRE((epilogue & 0xff) >= 0 && (epilogue & 0xff) <= 3, VP_ERR_BAD_ARG, "vp_gemm_bf16: bad epilogue %d", epilogue);
-  VP_REQUIRE(force_generic == 0 || force_generic == 1 || force_generic == 2 || force_generic == 3 || force_generic == 7 || force_generic == 8 ||
-                 force_generic == 13 || force_generic == 14, VP_ERR_BAD_ARG, "vp_gemm_bf16: unknown kernel selector %d", force_generic);
+  VP_REQUIRE(gemm_sel_known(force_generic), VP_ERR_BAD_ARG, "vp_gemm_bf16: unknown kernel selector %d", force_generic);
   GemmArgs p{(const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, (const bf16_t*)residual, M, N, K,
              lda, ldb, ldc, ldr, epilogue, 0, 0, nullptr, 0, nullptr, 0};
   p.dbg = vp_gemm_dbg();
-  const bool fast = (force_generic != 1) && (K % 64 == 0) && (lda % 8 == 0) && (ldb % 8 == 0) &&
-                    ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0;
-  const long big_tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  {
-    static int w4_env = -1;
-    if (w4_env < 0) { const char* e = getenv("VP_GEMM_W4"); w4_env = e ? atoi(e) : 1; }      // default since round 3 (VP_GEMM_W4=0: the 8-phase kernel)
-    const bool w4_ok = fast && M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && (big_tiles >= 192 || force_generic == 8) &&
-                       !bias && (epilogue & 0xff) == EPI_NONE && (((uintptr_t)C) & 15) == 0 &&
-                       (out_f32 ? (!residual && ldc % 4 == 0)
-                                : (ldc % 8 == 0 && ldc < (1L << 22) &&                       // (32-bit byte offsets inside a 128-row sub-tile)
-                                   (!residual || (ldr % 8 == 0 && ldr < (1L << 22) && (((uintptr_t)residual) & 15) == 0))));
-    // The 4-wave kernel walks its tiles statically.  Next to RCCL kernels (world > 1) a CU that a collective holds delays that block's share
-    // (tools/gemm_interference.py: up to 1.45x for the launches that overlap a collective); in the PT step that is the handful of GEMMs under the
-    // 0.2 GB gradient all-reduce, against 6-10 % on every launch with the 8-phase kernel and its per-XCD tile claims — so the multi-GPU step uses
-    // it too (VP_GEMM_W4=0 / VP_GEMM_W4=2 "only when no collective can run beside it" select the 8-phase kernel).
-    if (w4_ok && (force_generic == 8 || (force_generic == 0 && (w4_env == 1 || (w4_env == 2 && !sched_ws))))) {
-      p.c_nt = (!out_f32 && N <= 8192 && vp_c_nt_enabled()) ? 1 : 0;
-      static bool attr_w4 = false;
-      if (!attr_w4) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attr_w4 = true;
-      }
-      const unsigned g4 = (unsigned)(big_tiles > 256 ? 256 : big_tiles);
-      if (out_f32) hipLaunchKernelGGL(gemm_nt_256w4<true>, dim3(g4), dim3(256), 163840, stream, p);
-      else hipLaunchKernelGGL(gemm_nt_256w4<false>, dim3(g4), dim3(256), 163840, stream, p);
-      return vp_check_launch("vp_gemm_bf16");
-    }
-  }
-  {
-    // General variant of the 4-wave kernel (round 4; force code 14; VP_GEMM_W4G=0 turns the automatic choice off): bias / activation / residual /
-    // row-scale epilogues and an M tail, for the tower, projector, head and DPT launches that used to fall to the 8-phase kernel.
-    static int w4g_env = -1;
-    if (w4g_env < 0) { const char* e = getenv("VP_GEMM_W4G"); w4g_env = e ? atoi(e) : 1; }
-    const int epi8 = epilogue & 0xff;
-    const bool w4g_ok = fast && !out_f32 && N % 256 == 0 && K % 128 == 0 && M >= 256 && (((uintptr_t)C) & 15) == 0 && ldc % 8 == 0 && ldc < (1L << 22) &&
-                        (!bias || (((uintptr_t)bias) & 15) == 0) && !(residual && epi8 != EPI_NONE) &&
-                        (!residual || (ldr % 8 == 0 && ldr < (1L << 22) && (((uintptr_t)residual) & 15) == 0));
-    // erf-GELU launches stay on the 8-phase kernel: ~50 VALU instructions per element at one wave per SIMD cost more than the K loop gains
-    // (ConvNeXt fc1 18432 x 6144 x 1536: 861 -> 800 TF/s; bias / residual launches: 1092 -> 1363, 1062 -> 1440, 892 -> 1101 TF/s)
-    if (w4g_ok && (force_generic == 14 || (force_generic == 0 && w4g_env == 1 && big_tiles >= 64 && epi8 != EPI_GELU))) {     // (tools/vit_w4_probe.py: ahead of the 128-tile kernel from 76 tiles on)
-      static bool attr_w4g = false;
-      if (!attr_w4g) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attr_w4g = true;
-      }
-      const unsigned g4 = (unsigned)(big_tiles > 256 ? 256 : big_tiles);
-      hipLaunchKernelGGL((gemm_nt_256w4<false, 1>), dim3(g4), dim3(256), 163840, stream, p);
-      return vp_check_launch("vp_gemm_bf16");
-    }
-  }
-  if (fast && (force_generic == 7 || (force_generic == 0 && big_tiles >= 192 && M >= 256 && N >= 256))) {   // default large-problem kernel
-    static bool attr_p8 = false;
-    if (!attr_p8) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      attr_p8 = true;
-    }
-    // persistent (one block per CU streaming its output tiles) when the K-tile count is even (buffer parity is then the same
-    // for every output tile); otherwise one block per output tile
-    const unsigned g8 = (unsigned)(((K / 64) % 2 == 0 && big_tiles > 256 && !(p.dbg & 0x20000)) ? 256 : big_tiles);
-    if (g8 == 256) p.sched = sched_ws;
-    p.c_nt = (!out_f32 && N <= 8192 && (long)M * ldc * 2 < 0x7fffffffL && vp_c_nt_enabled()) ? 1 : 0;
-    if (out_f32) hipLaunchKernelGGL(gemm_nt_256p8<true>, dim3(g8), dim3(512), 131072, stream, p);
-    else if (vp_ph4_enabled() && force_generic == 0) {
-      static bool attr_p4 = false;
-      if (!attr_p4) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        attr_p4 = true;
-      }
-      hipLaunchKernelGGL((gemm_nt_256p8<false, true>), dim3(g8), dim3(512), 131072, stream, p);
-    } else hipLaunchKernelGGL(gemm_nt_256p8<false>, dim3(g8), dim3(512), 131072, stream, p);
-  } else if (fast && force_generic == 13 && !out_f32) {       // 4-phase variant of the 8-phase kernel (A/B testing)
-    (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    const unsigned g8 = (unsigned)(((K / 64) % 2 == 0 && big_tiles > 256 && !(p.dbg & 0x20000)) ? 256 : big_tiles);
-    hipLaunchKernelGGL((gemm_nt_256p8<false, true>), dim3(g8), dim3(512), 131072, stream, p);
-  } else if (fast && force_generic != 2 && (force_generic == 3 || (big_tiles >= 192 && M >= 256 && N >= 256))) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      attr_done = true;
-    }
-    const unsigned pgrid = (unsigned)(big_tiles < 256 ? big_tiles : 256);      // persistent: one block per CU
-    if (out_f32) hipLaunchKernelGGL(gemm_nt_256<true>, dim3(pgrid), dim3(512), 131072, stream, p);
-    else hipLaunchKernelGGL(gemm_nt_256<false>, dim3(pgrid), dim3(512), 131072, stream, p);
-  } else if (fast) {
-    const int grid = ((M + 127) / 128) * ((N + 127) / 128);
-    if (out_f32) hipLaunchKernelGGL(gemm_nt_128<true>, dim3(grid), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(gemm_nt_128<false>, dim3(grid), dim3(256), 0, stream, p);
-  } else {
-    const int grid = ((M + 63) / 64) * ((N + 63) / 64);
-    if (out_f32) hipLaunchKernelGGL(gemm_nt_generic<true>, dim3(grid), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(gemm_nt_generic<false>, dim3(grid), dim3(256), 0, stream, p);
-  }
-  return vp_check_launch("vp_gemm_bf16");
+  static const int w4g = vp_env_int("VP_GEMM_W4G", 1);
+  const GemmRoute r = gemm_route({M, N, K, lda, ldb, ldc, ldr, al16(A), al16(B), al16(C), al16(bias), al16(residual), bias != nullptr,
+                                  residual != nullptr, epilogue, out_f32, force_generic, sched_ws != nullptr, vp_w4_switch(), w4g,
+                                  vp_ph4_switch(), vp_c_nt_switch(), p.dbg});
+  if (r.sched) p.sched = sched_ws;
+  p.c_nt = r.c_nt;
+  return gemm_launch("vp_gemm_bf16", r.kernel, out_f32 != 0, r.grid, stream, p);
 }
 
 // Residual GEMM that also emits the statistics of the next RMSNorm (reference: HF LlamaDecoderLayer.forward, modeling_llama.py: residual +
@@ -2111,15 +2028,8 @@ int vp_gemm_bf16_sumsq(int M, int N, int K, const void* A, long lda, const void*
   GemmArgs p{(const bf16_t*)A, (const bf16_t*)B, C, nullptr, (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, EPI_NONE, 0, 0, nullptr, 0, nullptr, 0};
   p.dbg = vp_gemm_dbg();
   p.sumsq_part = sumsq_part;
-  p.c_nt = (N <= 8192 && vp_c_nt_enabled()) ? 1 : 0;
-  static bool attr_w4 = false;
-  if (!attr_w4) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    attr_w4 = true;
-  }
-  const long big_tiles = (long)(M / 256) * (N / 256);
-  hipLaunchKernelGGL((gemm_nt_256w4<false, 2>), dim3((unsigned)(big_tiles > 256 ? 256 : big_tiles)), dim3(256), 163840, stream, p);
-  return vp_check_launch("vp_gemm_bf16_sumsq");
+  p.c_nt = gemm_c_nt(false, N, vp_c_nt_switch());
+  return gemm_launch("vp_gemm_bf16_sumsq", GK_W4F, false, gemm_grid_persistent(gemm_big_tiles(M, N)), stream, p);
 }
 
 // QKV projection of a decoder layer with rotate-half RoPE in the epilogue (reference: HF LlamaAttention.forward, modeling_llama.py: q/k/v_proj, then
@@ -2131,7 +2041,6 @@ int vp_gemm_bf16_rope(int M, int N, int K, const void* A, long lda, const void* 
                       int rope_cols, const float* cos_t, const float* sin_t, const int* pos, int S, hipStream_t stream) {
   VP_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C && cos_t && sin_t && S > 0, VP_ERR_BAD_ARG, "vp_gemm_bf16_rope: bad operands");
   VP_REQUIRE(lda >= K && ldb >= K && ldc >= N && rope_cols >= 0 && rope_cols <= N, VP_ERR_BAD_ARG, "vp_gemm_bf16_rope: leading dims / rope_cols");
-  const long big_tiles = (long)((M + 255) / 256) * (N / 256);
   VP_REQUIRE(N % 256 == 0 && K % 128 == 0 && M >= 256 && rope_cols % 128 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && ldc < (1L << 22) &&
                  ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)cos_t) | ((uintptr_t)sin_t)) & 15) == 0,
              VP_ERR_UNSUPPORTED_SHAPE, "vp_gemm_bf16_rope: needs N %% 256 == 0, K %% 128 == 0, M >= 256, rope_cols %% 128 == 0, 16-byte aligned rows (got %d %d %d)", M, N, K);
@@ -2139,13 +2048,7 @@ int vp_gemm_bf16_rope(int M, int N, int K, const void* A, long lda, const void* 
   p.dbg = vp_gemm_dbg();
   p.rowscale = row_scale;
   p.rope_cos = cos_t; p.rope_sin = sin_t; p.rope_pos = pos; p.rope_S = S; p.rope_cols = rope_cols;
-  static bool attr_w4g = false;
-  if (!attr_w4g) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    attr_w4g = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_256w4<false, 1>), dim3((unsigned)(big_tiles > 256 ? 256 : big_tiles)), dim3(256), 163840, stream, p);
-  return vp_check_launch("vp_gemm_bf16_rope");
+  return gemm_launch("vp_gemm_bf16_rope", GK_W4G, false, gemm_grid_persistent(gemm_big_tiles(M, N)), stream, p);
 }
 
 // Fused SwiGLU GEMMs for the decoder MLP (reference: HF LlamaMLP.forward, modeling_llama.py — down(act(gate(x)) * up(x)); the
@@ -2176,44 +2079,10 @@ int vp_gemm_bf16_swiglu(int mode, int M, int N, int K, const void* A, long lda, 
     p.rowscale = (const float*)aux;
     p.aux = nullptr;
   }
-  const long big_tiles = (long)(M / 256) * (N / 256);
-  {
-    static int w4_env = -1;
-    if (w4_env < 0) { const char* e = getenv("VP_GEMM_W4"); w4_env = e ? atoi(e) : 1; }
-    if ((w4_env == 1 || (w4_env == 2 && !sched_ws)) && K % 128 == 0 && big_tiles >= 192 && ldc < (1L << 21) && ldc2 < (1L << 21) && ldaux < (1L << 21)) {   // same routing as vp_gemm_bf16
-      static bool attr_w4 = false;
-      if (!attr_w4) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attr_w4 = true;
-      }
-      if (p.rowscale) {
-        static bool attr_w4f = false;
-        if (!attr_w4f) {
-          (void)hipFuncSetAttribute((const void*)gemm_nt_256w4<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-          attr_w4f = true;
-        }
-        hipLaunchKernelGGL((gemm_nt_256w4<false, 2>), dim3((unsigned)(big_tiles > 256 ? 256 : big_tiles)), dim3(256), 163840, stream, p);
-      } else hipLaunchKernelGGL(gemm_nt_256w4<false>, dim3((unsigned)(big_tiles > 256 ? 256 : big_tiles)), dim3(256), 163840, stream, p);
-      return vp_check_launch("vp_gemm_bf16_swiglu");
-    }
-  }
-  VP_REQUIRE(!p.rowscale, VP_ERR_UNSUPPORTED_SHAPE, "vp_gemm_bf16_swiglu: the row scale exists on the one-wave-per-SIMD kernel only (K %% 128 == 0, >= 192 tiles; got %d %d %d)", M, N, K);
-  static bool attr_p8 = false;
-  if (!attr_p8) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    attr_p8 = true;
-  }
-  const unsigned g8 = (unsigned)(((K / 64) % 2 == 0 && big_tiles > 256) ? 256 : big_tiles);
-  if (g8 == 256) p.sched = sched_ws;
-  if (vp_ph4_enabled()) {
-    static bool attr_p4 = false;
-    if (!attr_p4) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256p8<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-      attr_p4 = true;
-    }
-    hipLaunchKernelGGL((gemm_nt_256p8<false, true>), dim3(g8), dim3(512), 131072, stream, p);
-  } else hipLaunchKernelGGL(gemm_nt_256p8<false>, dim3(g8), dim3(512), 131072, stream, p);
-  return vp_check_launch("vp_gemm_bf16_swiglu");
+  const GemmRoute r = gemm_route_swiglu(M, N, K, ldc, ldc2, ldaux, p.rowscale != nullptr, sched_ws != nullptr, vp_w4_switch(), vp_ph4_switch());
+  VP_REQUIRE(r.kernel != GK_NONE, VP_ERR_UNSUPPORTED_SHAPE, "vp_gemm_bf16_swiglu: the row scale exists on the one-wave-per-SIMD kernel only (K %% 128 == 0, >= 192 tiles; got %d %d %d)", M, N, K);
+  if (r.sched) p.sched = sched_ws;
+  return gemm_launch("vp_gemm_bf16_swiglu", r.kernel, false, r.grid, stream, p);
 }
 
 // C[M,N] (+)= A[K,M]^T B[K,N]: both operands contraction-major, i.e. the weight gradient dW[out,in] = dY[tokens,out]^T X[tokens,in]
@@ -2231,26 +2100,16 @@ int vp_gemm_tn_bf16(int M, int N, int K, const void* A, long lda, const void* B,
   VP_REQUIRE(!accumulate || out_f32, VP_ERR_BAD_ARG, "vp_gemm_tn_bf16: accumulate needs fp32 output");
   GemmArgs p{(const bf16_t*)A, (const bf16_t*)B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, EPI_NONE, 0,
              accumulate ? 3 : 0, nullptr, 0, nullptr, 0};
-  static bool attr_tn = false;
-  if (!attr_tn) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_256p8<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_256p8<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    attr_tn = true;
-  }
-  const long big_tiles = (long)(M / 256) * (N / 256);
-  const unsigned g8 = (unsigned)(((K / 64) % 2 == 0 && big_tiles > 256) ? 256 : big_tiles);
+  const unsigned g8 = gemm_grid_p8(K, gemm_big_tiles(M, N));
   if (g8 == 256) p.sched = sched_ws;
-  if (out_f32) hipLaunchKernelGGL(gemm_tn_256p8<true>, dim3(g8), dim3(512), 131072, stream, p);
-  else hipLaunchKernelGGL(gemm_tn_256p8<false>, dim3(g8), dim3(512), 131072, stream, p);
-  return vp_check_launch("vp_gemm_tn_bf16");
+  return gemm_launch("vp_gemm_tn_bf16", GK_TN, out_f32 != 0, g8, stream, p);
 }
 
 
 int vp_transpose_bf16(int rows, int cols, const void* in, long ld_in, void* out, long ld_out, hipStream_t stream) {
   VP_REQUIRE(rows > 0 && cols > 0 && in && out, VP_ERR_BAD_ARG, "vp_transpose_bf16: bad args");
   dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-  hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, rows, cols,
-                     ld_in, ld_out, 0L, 0L);
+  vp_launch<transpose_bf16_kernel>(grid, dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, rows, cols, ld_in, ld_out, 0L, 0L);
   return vp_check_launch("vp_transpose_bf16");
 }
 
@@ -2259,8 +2118,8 @@ int vp_transpose_batched_bf16(int batch, int rows, int cols, const void* in, lon
   VP_REQUIRE(batch > 0 && batch <= 65535 && rows > 0 && cols > 0 && in && out, VP_ERR_BAD_ARG, "vp_transpose_batched_bf16: bad args");
   VP_REQUIRE(batch_stride_in % 8 == 0 && batch_stride_out % 8 == 0, VP_ERR_BAD_ARG, "vp_transpose_batched_bf16: batch strides must be multiples of 8 elements");
   dim3 grid((cols + 63) / 64, (rows + 63) / 64, batch);
-  hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, rows, cols, ld_in, ld_out,
-                     batch_stride_in, batch_stride_out);
+  vp_launch<transpose_bf16_kernel>(grid, dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, rows, cols, ld_in, ld_out, batch_stride_in,
+                                   batch_stride_out);
   return vp_check_launch("vp_transpose_batched_bf16");
 }
 

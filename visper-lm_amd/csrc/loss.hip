@@ -128,7 +128,7 @@ int vp_ce_fwd_bwd(long rows, int V, void* logits, long ld, const long* labels, f
                   hipStream_t s) {
   VP_REQUIRE(rows > 0 && V > 0 && logits && labels && row_loss, VP_ERR_BAD_ARG, "vp_ce_fwd_bwd: bad args");
   VP_REQUIRE(ld % 8 == 0, VP_ERR_UNSUPPORTED_SHAPE, "vp_ce_fwd_bwd: ld must be a multiple of 8");
-  static const bool reg_path = [] { const char* e = getenv("VP_CE_REG"); return !e || atoi(e) != 0; }();
+  static const int reg_path = vp_env_int("VP_CE_REG", 1);
   const int nch = ((V >> 3) + 511) / 512;
   if (reg_path && V % 8 == 0 && nch <= 32) {            // the row fits the block's registers: one read of the logits instead of two
 #define VP_CE_REG(N) hipLaunchKernelGGL(ce_fwd_bwd_reg_kernel<N>, dim3((unsigned)rows), dim3(512), 0, s, (bf16_t*)logits, labels, row_loss, V, ld, grad_scale, write_grad)

@@ -3,6 +3,7 @@
 #include "common.h"
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 static thread_local char g_err[512] = "";
 
@@ -20,6 +21,11 @@ int vp_check_launch(const char* what) {
     return VP_ERR_HIP;
   }
   return VP_OK;
+}
+
+int vp_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 extern "C" {

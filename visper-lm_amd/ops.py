@@ -76,6 +76,66 @@ def _rows2d(t):
 
 
 # ------------------------------------------------------------------------------------------------
+class _gemm_prof:
+    """`with _gemm_prof(M, N, K, tag):` around one GEMM launch: while GEMM_PROF is a list (bench.py and tools/step_gemm_profile.py assign it from
+    outside) the launch is bracketed by HIP events on its stream and (e0, e1, flops, (M, N, K), tag) is appended; otherwise nothing happens."""
+    __slots__ = ("rec", "e0")
+
+    def __init__(self, M, N, K, tag):
+        self.rec = (2.0 * M * N * K, (M, N, K), tag)
+
+    def __enter__(self):
+        self.e0 = None
+        if GEMM_PROF is not None:
+            self.e0 = torch.cuda.Event(enable_timing=True)
+            self.e0.record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.e0 is not None and exc_type is None and GEMM_PROF is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            GEMM_PROF.append((self.e0, e1) + self.rec)
+
+
+# Which fused GEMM entry point takes a shape: the Python mirrors of the C routing (csrc/gemm_route.h, and the VP_REQUIREs of the entry points in
+# csrc/gemm.hip).  The engine asks these before it plans a layer; a shape they admit and the library refuses is an error, not a fallback.
+# They read os.environ on every call (bench.py flips switches in-process).
+GEMM_TILE = 256         # M, N % 256 == 0: whole 256 x 256 output tiles (vp_gemm_bf16_swiglu / _sumsq / vp_gemm_tn_bf16; N alone for vp_gemm_bf16_rope)
+P8_K_MULTIPLE = 64      # K % 64 == 0: the 8-phase kernels' K-tile (vp_gemm_bf16_swiglu, vp_gemm_tn_bf16)
+W4_K_MULTIPLE = 128     # K % 128 == 0: the one-wave-per-SIMD kernels' K-tile (w4_ok / w4g_ok in gemm_route, vp_gemm_bf16_rope, vp_gemm_bf16_sumsq)
+W4G_MIN_TILES = 64      # big_tiles >= 64: from where gemm_route picks the general one-wave-per-SIMD kernel by itself
+W4_MIN_TILES = 192      # big_tiles >= 192: from where gemm_route / gemm_route_swiglu pick the lean one-wave-per-SIMD kernel
+
+
+def gemm_rowscale_ok(M, N, K):
+    """Shapes vp_gemm_bf16_rope accepts as a plain row-scaled GEMM (rope_cols = 0): the general variant of the one-wave-per-SIMD kernel."""
+    return (N % GEMM_TILE == 0 and K % W4_K_MULTIPLE == 0 and M >= GEMM_TILE and ((M + 255) // 256) * (N // 256) >= W4G_MIN_TILES
+            and os.environ.get("VP_GEMM_ROPE", "1") != "0")
+
+
+def gemm_rope_ok(M, N, K, head_dim):
+    """Shapes vp_gemm_bf16_rope accepts WITH the rotation in its epilogue (whole 128-wide heads per wave sub-tile)."""
+    return head_dim == 128 and gemm_rowscale_ok(M, N, K)
+
+
+def fold_norm_ok(M, H, I, head_dim, nqkv):
+    """Shapes for which a decoder layer can run with RMSNorm folded away (gamma in the frozen weights, 1/rms as a row scale in the consuming
+    GEMM's epilogue, sums of squares from the producing residual GEMM's epilogue): every GEMM involved must be a one-wave-per-SIMD launch."""
+    return (gemm_rowscale_ok(M, nqkv, H) and head_dim in (96, 128) and M % GEMM_TILE == 0 and H % GEMM_TILE == 0 and I % W4_K_MULTIPLE == 0
+            and (M // 256) * (2 * I // 256) >= W4_MIN_TILES
+            and os.environ.get("VP_GEMM_W4", "1") == "1" and os.environ.get("VP_FOLD_NORM", "1") != "0")
+
+
+def swiglu_fusable(M, N, K):
+    """Shapes the fused SwiGLU GEMM epilogues accept (vp_gemm_bf16_swiglu: 8-phase kernel, interior tiles only)."""
+    return M % GEMM_TILE == 0 and N % GEMM_TILE == 0 and K % P8_K_MULTIPLE == 0
+
+
+def gemm_tn_ok(M, N, K):
+    """Shapes the TN (transpose-free weight-gradient) kernel takes."""
+    return M % GEMM_TILE == 0 and N % GEMM_TILE == 0 and K % P8_K_MULTIPLE == 0
+
+
 def gemm(a, w, bias=None, residual=None, epi=EPI_NONE, out=None, out_f32=False, force_generic=False):
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias) + residual.
     force_generic: 0 auto | 1 bounds-checked generic kernel | 2 the 128-tile kernel | 3 the simple persistent 256-tile kernel |
@@ -91,25 +151,10 @@ def gemm(a, w, bias=None, residual=None, epi=EPI_NONE, out=None, out_f32=False, 
     ldr = 0
     if residual is not None:
         _, _, ldr = _rows2d(residual)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_bf16", M, N, K, _p(a), lda, _p(w), ldb, _p(out), ldc, _p(bias), _p(residual), ldr, epi,
-              1 if out.dtype == torch.float32 else 0, int(force_generic), _sched(), _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "nt_lean" if (bias is None and epi == 0) else "nt_epi"))
+    with _gemm_prof(M, N, K, "nt_lean" if (bias is None and epi == 0) else "nt_epi"):
+        _lib.call("vp_gemm_bf16", M, N, K, _p(a), lda, _p(w), ldb, _p(out), ldc, _p(bias), _p(residual), ldr, epi,
+                  1 if out.dtype == torch.float32 else 0, int(force_generic), _sched(), _stream())
     return out
-
-
-def gemm_rowscale_ok(M, N, K):
-    """Shapes vp_gemm_bf16_rope accepts as a plain row-scaled GEMM (rope_cols = 0): the general variant of the one-wave-per-SIMD kernel."""
-    return N % 256 == 0 and K % 128 == 0 and M >= 256 and ((M + 255) // 256) * (N // 256) >= 64 and os.environ.get("VP_GEMM_ROPE", "1") != "0"
-
-
-def gemm_rope_ok(M, N, K, head_dim):
-    """Shapes vp_gemm_bf16_rope accepts WITH the rotation in its epilogue (whole 128-wide heads per wave sub-tile)."""
-    return head_dim == 128 and gemm_rowscale_ok(M, N, K)
 
 
 def gemm_rope(a, w, S, rope_cols, cos_t, sin_t, pos=None, row_scale=None):
@@ -118,21 +163,9 @@ def gemm_rope(a, w, S, rope_cols, cos_t, sin_t, pos=None, row_scale=None):
     N, K2, ldb = _rows2d(w)
     assert K == K2 and a.dtype == BF16 and w.dtype == BF16 and cos_t.dtype == torch.float32 and (rope_cols == 0 or cos_t.shape[-1] == 64)
     out = torch.empty(*a.shape[:-1], N, device=a.device, dtype=BF16)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_bf16_rope", M, N, K, _p(a), lda, _p(w), ldb, _p(out), N, _p(row_scale), rope_cols, _p(cos_t), _p(sin_t), _p(pos), S, _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "nt_rope"))
+    with _gemm_prof(M, N, K, "nt_rope"):
+        _lib.call("vp_gemm_bf16_rope", M, N, K, _p(a), lda, _p(w), ldb, _p(out), N, _p(row_scale), rope_cols, _p(cos_t), _p(sin_t), _p(pos), S, _stream())
     return out
-
-
-def fold_norm_ok(M, H, I, head_dim, nqkv):
-    """Shapes for which a decoder layer can run with RMSNorm folded away (gamma in the frozen weights, 1/rms as a row scale in the consuming
-    GEMM's epilogue, sums of squares from the producing residual GEMM's epilogue): every GEMM involved must be a one-wave-per-SIMD launch."""
-    return (gemm_rowscale_ok(M, nqkv, H) and head_dim in (96, 128) and M % 256 == 0 and H % 256 == 0 and I % 128 == 0 and (M // 256) * (2 * I // 256) >= 192
-            and os.environ.get("VP_GEMM_W4", "1") == "1" and os.environ.get("VP_FOLD_NORM", "1") != "0")
 
 
 def gemm_sumsq(a, w, residual):
@@ -143,13 +176,8 @@ def gemm_sumsq(a, w, residual):
     out = torch.empty(*a.shape[:-1], N, device=a.device, dtype=BF16)
     part = torch.empty(M, N // 16, device=a.device, dtype=torch.float32)
     _, _, ldr = _rows2d(residual)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_bf16_sumsq", M, N, K, _p(a), lda, _p(w), ldb, _p(out), N, _p(residual), ldr, _p(part), _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "nt_fold"))
+    with _gemm_prof(M, N, K, "nt_fold"):
+        _lib.call("vp_gemm_bf16_sumsq", M, N, K, _p(a), lda, _p(w), ldb, _p(out), N, _p(residual), ldr, _p(part), _stream())
     return out, part
 
 
@@ -158,11 +186,6 @@ def rstd_from_sumsq(part, H, eps):
     rstd = torch.empty(M, device=part.device, dtype=torch.float32)
     _lib.call("vp_rstd_from_sumsq", M, nparts, _p(part), H, float(eps), _p(rstd), _stream())
     return rstd
-
-
-def swiglu_fusable(M, N, K):
-    """Shapes the fused SwiGLU GEMM epilogues accept (vp_gemm_bf16_swiglu: 8-phase kernel, interior tiles only)."""
-    return M % 256 == 0 and N % 256 == 0 and K % 64 == 0
 
 
 def interleave_gate_up(w_gate_up):
@@ -183,13 +206,8 @@ def gemm_swiglu_fwd(a, w_gu, row_scale=None):
     assert K == K2 and swiglu_fusable(M, N, K)
     gu = torch.empty(*a.shape[:-1], N, device=a.device, dtype=BF16)
     act = torch.empty(*a.shape[:-1], N // 2, device=a.device, dtype=BF16)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_bf16_swiglu", 1, M, N, K, _p(a), lda, _p(w_gu), ldb, _p(gu), N, _p(act), N // 2, _p(row_scale), 0, _sched(), _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "nt_lean" if row_scale is None else "nt_fold"))
+    with _gemm_prof(M, N, K, "nt_lean" if row_scale is None else "nt_fold"):
+        _lib.call("vp_gemm_bf16_swiglu", 1, M, N, K, _p(a), lda, _p(w_gu), ldb, _p(gu), N, _p(act), N // 2, _p(row_scale), 0, _sched(), _stream())
     return gu, act
 
 
@@ -199,20 +217,10 @@ def gemm_swiglu_bwd(dy, w_down_T, gate_up):
     N, K2, ldb = _rows2d(w_down_T)
     assert K == K2 and swiglu_fusable(M, N, K) and gate_up.shape[-1] == 2 * N and gate_up.is_contiguous()
     dgu = torch.empty_like(gate_up)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_bf16_swiglu", 2, M, N, K, _p(dy), lda, _p(w_down_T), ldb, _p(dgu), 2 * N, None, 0, _p(gate_up), 2 * N,
-              _sched(), _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "nt_lean"))
+    with _gemm_prof(M, N, K, "nt_lean"):
+        _lib.call("vp_gemm_bf16_swiglu", 2, M, N, K, _p(dy), lda, _p(w_down_T), ldb, _p(dgu), 2 * N, None, 0, _p(gate_up), 2 * N,
+                  _sched(), _stream())
     return dgu
-
-
-def gemm_tn_ok(M, N, K):
-    """Shapes the TN (transpose-free weight-gradient) kernel takes."""
-    return M % 256 == 0 and N % 256 == 0 and K % 64 == 0
 
 
 def gemm_tn(a, b, out=None, out_f32=True, accumulate=False):
@@ -224,13 +232,8 @@ def gemm_tn(a, b, out=None, out_f32=True, accumulate=False):
         assert not accumulate
         out = torch.empty(M, N, device=a.device, dtype=torch.float32 if out_f32 else BF16)
     assert out.stride(-1) == 1 and out.dtype == (torch.float32 if out_f32 else BF16)
-    if GEMM_PROF is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.call("vp_gemm_tn_bf16", M, N, K, _p(a), lda, _p(b), ldb, _p(out), out.stride(0), int(out_f32), int(accumulate), _sched(), _stream())
-    if GEMM_PROF is not None:
-        e1.record()
-        GEMM_PROF.append((e0, e1, 2.0 * M * N * K, (M, N, K), "tn"))
+    with _gemm_prof(M, N, K, "tn"):
+        _lib.call("vp_gemm_tn_bf16", M, N, K, _p(a), lda, _p(b), ldb, _p(out), out.stride(0), int(out_f32), int(accumulate), _sched(), _stream())
     return out
 
 
