@@ -221,6 +221,24 @@ int vp_attn_bwd_rope(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void*
 long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue);
 int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual, long ldr,
                    const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, vp_stream_t stream);
+/* FP8 weight-only decoding.  The reference loads a checkpoint for evaluation in 8 / 4 bits with load_pretrained_model(..., load_8bit, load_4bit)
+ * (ola_vlm/model/builder.py:26-34: bitsandbytes); these two entry points stand in for that on gfx950 with OCP e4m3fn weights (not the MI300
+ * fnuz encoding) and one power-of-two fp32 scale per weight row.
+ * vp_quant_rows_e4m3: W bf16 [N, K] (finite) -> Q uint8 [N, K] e4m3fn bytes + scale fp32 [N].  Per row: s = 2^ceil(log2(absmax / 448)) (rows of
+ *   zeros: s = 1), Q = e4m3fn(W / s) rounded to nearest even as torch's .to(torch.float8_e4m3fn) does on the CPU; the row's largest magnitude
+ *   lands in (224, 448] before rounding, so nothing saturates and no byte is NaN.  writeback != 0: W is overwritten in place with bf16(Q * s),
+ *   which is exact (the bf16 kernels on the written-back weights and vp_decode_gemm_w8 on Q then compute the same model).  Row order only:
+ *   weight layouts (interleaved gate|up, halves, folded norms) need no support, the scale travels with the row.  K, ldw, ldq multiples of 8
+ *   (ldw in elements, ldq in bytes), W 16-byte and Q 8-byte aligned.
+ * vp_decode_gemm_w8: vp_decode_gemm with W = uint8 [N, K] e4m3fn bytes (ldw in bytes) and w_scale fp32 [N]: the bytes are converted exactly to
+ *   bf16 in registers and fed to the same MFMA against the bf16 activation (A is not quantised); row n's fp32 sum is multiplied by w_scale[n]
+ *   before any rounding point of the epilogue (SwiGLU: the gate and the up sum each by their own row's scale).  Same prologue, epilogues,
+ *   split-K contract (its own vp_decode_gemm_w8_workspace_bytes) and error codes as vp_decode_gemm; K and ldw multiples of 16. */
+int vp_quant_rows_e4m3(int N, int K, void* W, long ldw, void* Q, long ldq, float* scale, int writeback, vp_stream_t stream);
+long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
+                      const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                      vp_stream_t stream);
 /* RoPE of the new token and the KV append (HF apply_rotary_pos_emb + DynamicCache.update, modeling_llama.py, at position pos[b] of each
  * sequence): qkv [B, ldqkv] rows (Hq q heads | Hkv k heads | Hkv v heads, head_dim D); q rotated into q_out [B, ldq]; k rotated and v copied
  * into row pos[b] of the caches ([B, Smax, Hkv, D] views, strides in elements).  cos_t / sin_t: fp32 [>= Smax, D/2] (ops.rope_tables); pos:

@@ -5,6 +5,13 @@ one JSON line (and writes it to --out).  Kernel times come from a separate `rocp
 
   python tools/decode_bench.py --model llama3 --out profiles/decode_bench_llama3.json
   python tools/decode_bench.py --model phi3 --out profiles/decode_bench_phi3.json
+
+--weights fp8: the decoder (and lm_head) is quantised to FP8 weight-only form first (Engine.quantize_decoder, with write-back), then every
+batch size runs the bf16 leg (the fp8 copies hidden: the bf16 kernels on the written-back weights) and the fp8 leg alternately, --repeats
+times each, in this one process on the same engine and prompts; the JSON carries both legs, their medians, the spread (max - min) of the
+bf16 leg and the ratio.  A gain counts only where the fp8 median is below the bf16 median by more than that spread.
+
+  python tools/decode_bench.py --model llama3 --weights fp8 --out profiles/decode_bench_llama3_fp8.json
 """
 import argparse
 import json
@@ -71,6 +78,29 @@ def time_decode(eng, B, new, text_tokens, use_graph):
                 host_enqueue_ms_per_token_median=round(enq[len(enq) // 2], 4), graph=use_graph, tokens_timed=new - 1)
 
 
+def fp8_legs(eng, B, new, text_tokens, repeats, use_graph):
+    """bf16 leg and fp8 leg alternately on the quantised engine -> dict with every run, the medians, the bf16 spread and the ratio"""
+    fq = eng.fq
+    assert fq is not None
+    legs = {"bf16": [], "fp8": []}
+    for _ in range(repeats):
+        for leg in ("bf16", "fp8"):
+            eng.fq = None if leg == "bf16" else fq
+            try:
+                r = time_decode(eng, B, new, text_tokens, use_graph)
+            finally:
+                eng.fq = fq
+            r["weights"] = leg
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    tb, t8 = [r["ms_per_token"] for r in legs["bf16"]], [r["ms_per_token"] for r in legs["fp8"]]
+    spread = max(tb) - min(tb)
+    return dict(B=B, graph=use_graph, repeats=repeats, bf16_ms_per_token=tb, fp8_ms_per_token=t8, bf16_median=med(tb), fp8_median=med(t8),
+                bf16_spread=round(spread, 4), fp8_over_bf16=round(med(t8) / med(tb), 4), gain_ms=round(med(tb) - med(t8), 4),
+                gain_exceeds_bf16_spread=bool(med(tb) - med(t8) > spread), runs=legs["bf16"] + legs["fp8"])
+
+
 def weight_bytes(eng):
     cfg = eng.cfg
     H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
@@ -87,6 +117,9 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--profile", action="store_true", help="graph on only (for a rocprofv3 --kernel-trace --stats run)")
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8"], help="fp8: bf16 leg, then fp8 leg, on the same quantised engine")
+    ap.add_argument("--repeats", type=int, default=3, help="--weights fp8: runs of each leg, alternating")
+    ap.add_argument("--graph", action="store_true", help="--weights fp8: time the captured step instead of eager launches")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
@@ -94,7 +127,22 @@ def main():
     dec_b, head_b = weight_bytes(eng)
     res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
                roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
-    for B in [int(x) for x in a.batches.split(",")]:
+    if a.weights == "fp8":
+        eng.quantize_decoder(lm_head=True)
+        res.update(weights="fp8", lm_head_fp8=True, fp8_roofline_ms_per_token_8tbps=round((dec_b + head_b) / 2 / 8e12 * 1e3, 3), cells=[])
+        for B in [int(x) for x in a.batches.split(",")]:
+            if a.profile:                                         # kernel-trace run: the fp8 leg alone, captured step
+                r = time_decode(eng, B, a.new, a.text, True)
+                r["weights"] = "fp8"
+                res["runs"].append(r)
+                print(json.dumps(r), flush=True)
+                continue
+            cell = fp8_legs(eng, B, a.new, a.text, a.repeats, a.graph)
+            cell["fp8_weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 2 / 8e12 * 1e3 / cell["fp8_median"], 3)
+            cell["bf16_weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 8e12 * 1e3 / cell["bf16_median"], 3)
+            res["runs"] += cell.pop("runs")
+            res["cells"].append(cell)
+    for B in ([] if a.weights == "fp8" else [int(x) for x in a.batches.split(",")]):
         for g in ((True,) if a.profile else (True, False)):
             r = time_decode(eng, B, a.new, a.text, g)
             kv_bytes_per_pos = 2 * 2 * eng.cfg.num_key_value_heads * eng.cfg.head_dim * eng.cfg.num_hidden_layers

@@ -64,6 +64,11 @@ def kernels(path):
     return res
 
 
+def matching(path, substrings):
+    """{kernel name: metadata} of the kernels whose (demangled) name contains one of `substrings`"""
+    return {n: d for n, d in kernels(path).items() if any(s in n for s in substrings)}
+
+
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 

@@ -11,6 +11,7 @@
 //  - decode_attn_split_kernel + decode_attn_combine_kernel: one query row per sequence, the Hq/Hkv heads of a KV head share every
 //    K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
 #include "common.h"
+#include "fp8_e4m3.h"
 
 #define VP_EPI_NONE 0
 #define VP_EPI_SWIGLU_IL 4      // SwiGLU on the interleaved gate|up rows (8 gate rows, 8 up rows, ...)
@@ -166,6 +167,241 @@ __global__ __launch_bounds__(256) void decode_gemm_combine_kernel(DecGemmArgs p)
   float v = 0.f;
   for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
   dg_store(p, m, n, v, 0.f);
+}
+
+// ---------------------------------------------------------------- FP8 weight-only decode ---------------
+// The reference loads a checkpoint for evaluation in 8 / 4 bits through bitsandbytes (ola_vlm/model/builder.py:26-34, load_8bit / load_4bit);
+// gfx950's native answer is OCP e4m3fn weights with one power-of-two fp32 scale per row (fp8_e4m3.h, quant.py: the contract), converted
+// exactly to bf16 in registers: a 16-byte load then carries 16 weights instead of 8 and the skinny GEMM streams half the bytes.
+//  - quant_rows_e4m3_kernel: one block per row: absmax -> scale -> bytes (+ the dequantised value written back over the bf16 row).
+//  - decode_gemm_w8_kernel: decode_gemm_kernel's structure (one 16-row W tile per block, K over the 4 waves and KS blocks, the same MFMA with
+//    the same k permutation on both operands, the same prologue / epilogues through dg_norm / dg_store); a wave consumes 512 k per chunk =
+//    8 loads of 16 fp8 per lane, each feeding two MFMAs.  The next chunk's 8 loads are issued before the current chunk is converted, and
+//    the first chunk's before the rstd pass of the norm prologue, so the conversion (one v_cvt_scalef32_pk_bf16_fp8 per pair) never waits
+//    with no load in flight.  Row n's fp32 sum is multiplied by w_scale[n] before the epilogue's first rounding point.
+__global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(bf16_t* __restrict__ W, long ldw, uint8_t* __restrict__ Q, long ldq,
+                                                              float* __restrict__ scale, int K, int writeback) {
+  __shared__ uint32_t red[4];
+  const long n = blockIdx.x;
+  bf16_t* wr = W + n * ldw;
+  uint8_t* qr = Q + n * ldq;
+  uint32_t am = 0;
+  for (int k = threadIdx.x * 8; k < K; k += 256 * 8) {
+    const bf16x8 v = *(const bf16x8*)(wr + k);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[j] & 0x7fffu);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
+  __syncthreads();
+  am = max(max(red[0], red[1]), max(red[2], red[3]));
+  const int se = vp_e4m3_scale_exp(am);
+  if (threadIdx.x == 0) scale[n] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
+  for (int k = threadIdx.x * 8; k < K; k += 256 * 8) {
+    const bf16x8 v = *(const bf16x8*)(wr + k);
+    bf16x8 d;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t q = vp_e4m3_quant((uint16_t)v[j], se);
+      if (j < 4) lo |= q << (8 * j); else hi |= q << (8 * (j - 4));
+      d[j] = (short)vp_e4m3_dequant_bf16(q, se);
+    }
+    const u32x2 qv = {lo, hi};
+    *(u32x2*)(qr + k) = qv;
+    if (writeback) *(bf16x8*)(wr + k) = d;
+  }
+}
+
+static constexpr int DG8_KCHUNK = 512;       // K elements one wave consumes per iteration: 8 loads x 4 lane groups x 16 fp8
+
+struct DecGemmW8Args {
+  DecGemmArgs g;                             // g.W = the fp8 bytes, g.ldw in bytes
+  const float* wscale;
+};
+
+static int dg8_ksplit(int N, int K, int epi) {
+  const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
+  int ks = 1;
+  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG8_KCHUNK) == 0) ks *= 2;
+  return ks;
+}
+
+// 16 e4m3fn bytes -> two MFMA fragments (bytes 0..7 | bytes 8..15), exact.  gfx950 converts a pair of fp8 straight to a bf16 pair
+// (v_cvt_scalef32_pk_bf16_fp8 with scale 1: one instruction per two weights)
+__device__ __forceinline__ void dg8_cvt(const u32x4 q, bf16x8& lo, bf16x8& hi) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  u32x4 a, b;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bf16x2_t x = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[i], 1.0f, false), y = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[i], 1.0f, true);
+    if (i < 2) { a[2 * i] = __builtin_bit_cast(uint32_t, x); a[2 * i + 1] = __builtin_bit_cast(uint32_t, y); }
+    else { b[2 * (i - 2)] = __builtin_bit_cast(uint32_t, x); b[2 * (i - 2) + 1] = __builtin_bit_cast(uint32_t, y); }
+  }
+  lo = __builtin_bit_cast(bf16x8, a);
+  hi = __builtin_bit_cast(bf16x8, b);
+}
+
+// L of the 8 loads of one lane (16 k each, 64 apart: the 4 lane groups of a row read 64 consecutive bytes per load instruction, so one
+// instruction touches 16 half cache lines instead of 64 sixteen-byte pieces).  Past kend (a K range that is no multiple of the chunk; K and
+// Kc are multiples of 16) a load re-reads the range's last 16 bytes and its value becomes zero: no load is conditional, every address lies
+// inside the row
+template <int L>
+__device__ __forceinline__ void dg8_load(u32x4* wq, const uint8_t* wr, int k0, int kend, bool full) {
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < L; ++u) wq[u] = __builtin_nontemporal_load((const u32x4*)(wr + k0 + u * 64));
+  } else {
+#pragma unroll
+    for (int u = 0; u < L; ++u) {
+      const bool ok = k0 + u * 64 < kend;
+      const u32x4 v = __builtin_nontemporal_load((const u32x4*)(wr + (ok ? k0 + u * 64 : kend - 16)));
+      wq[u] = v & (ok ? ~0u : 0u);
+    }
+  }
+}
+
+// One lane's share of a chunk: 16 MFMAs on the 8 converted loads of wq, in parts of L loads (4; 2 with the norm prologue, whose gamma
+// vectors need the registers).  Each part issues its 2 L A fragments (bf16, L2-resident; + gamma) FIRST and then L loads of the next chunk
+// (wn, when there is one): the memory counter retires in order, so waiting for A leaves those W loads in flight under the conversion.  Past
+// kend A re-reads valid elements (clamped address) against zero weights.
+// NEXT: 0 = no next chunk, 1 = a whole one, 2 = a partial one (a template parameter: each case is its own straight-line code, so the
+// memory-counter waits are exact for it instead of the minimum over the cases)
+template <bool NORM, int NEXT>
+__device__ __forceinline__ f32x4 dg8_chunk(f32x4 acc, const u32x4* wq, u32x4* wn, const DecGemmArgs& p, const uint8_t* wr, const bf16_t* ar,
+                                           float rs, int k0, int kend, bool full) {
+  constexpr int L = NORM ? 2 : 4;
+#pragma unroll
+  for (int h = 0; h < 8 / L; ++h) {
+    bf16x8 av[2 * L], gv[2 * L];
+#pragma unroll
+    for (int u = 0; u < 2 * L; ++u) {
+      int k = k0 + (h * L + (u >> 1)) * 64 + (u & 1) * 8;          // the two halves of load h * L + u / 2
+      if (!full) k = min(k, kend - 8);
+      av[u] = *(const bf16x8*)(ar + k);
+      if (NORM) gv[u] = *(const bf16x8*)(p.gamma + k);
+    }
+    if (NEXT) dg8_load<L>(wn + L * h, wr, k0 + 4 * DG8_KCHUNK + h * L * 64, kend, NEXT == 1);
+    __builtin_amdgcn_sched_barrier(0);                           // the loads above stay above: no conversion is hoisted over them (registers)
+#pragma unroll
+    for (int u = 0; u < L; ++u) {
+      if (NORM) {
+#pragma unroll
+        for (int v = 2 * u; v < 2 * u + 2; ++v) av[v] = dg_norm(av[v], (const bf16_t*)&gv[v], rs);
+      }
+      u32x4 wv = wq[h * L + u];
+      asm volatile("" : "+v"(wv));                                 // pins the conversion below the loads of its own part: hoisted to the loop top it
+      bf16x8 lo, hi;                                              // would hold all 16 fragments of the chunk at once
+      dg8_cvt(wv, lo, hi);
+      // D[n][m] += sum_k W[n][k] A[m][k]: both operands carry the same k permutation (lane group g owns 16 k of every 64 of the chunk)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, av[2 * u], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, av[2 * u + 1], acc, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return acc;
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(DG_THREADS, 3) void decode_gemm_w8_kernel(DecGemmW8Args q) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16];
+  const DecGemmArgs& p = q.g;
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  // rows past N / M are clamped to the last valid row: their results are never stored, so the hot loop needs no masks
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const int m = min(r, p.M - 1);
+  const uint8_t* wr = (const uint8_t*)p.W + (long)n * p.ldw;
+  const bf16_t* ar = p.A + (long)m * p.lda;
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  int c = kbeg + w * DG8_KCHUNK;
+  u32x4 w0[8], w1[8];                                            // ping-pong: one chunk converts while the next one streams
+  if (c < kend) dg8_load<8>(w0, wr, c + g * 16, kend, c + DG8_KCHUNK <= kend);       // the first chunk is in flight under the rstd pass
+  if (NORM) {
+    // rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical)
+    for (int mm = w; mm < p.M; mm += 4) {
+      const bf16_t* a2 = p.A + (long)mm * p.lda;
+      float ss = 0.f;
+      for (int e = lane * 8; e < p.K; e += 512) {
+        const bf16x8 v = *(const bf16x8*)(a2 + e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
+      }
+      ss = wave_sum(ss);
+      if (lane == 0) rstd_s[mm] = rsqrtf(ss / (float)p.K + p.eps);
+    }
+    __syncthreads();
+  }
+  const float rs = NORM ? rstd_s[m] : 1.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#define DG8_STEP(WQ, WN)                                                                                          \
+  {                                                                                                               \
+    const int cn = c + 4 * DG8_KCHUNK, k0 = c + g * 16;                                                           \
+    const bool full = c + DG8_KCHUNK <= kend;                                                                     \
+    if (cn >= kend) acc = dg8_chunk<NORM, 0>(acc, WQ, WN, p, wr, ar, rs, k0, kend, full);                         \
+    else if (cn + DG8_KCHUNK <= kend) acc = dg8_chunk<NORM, 1>(acc, WQ, WN, p, wr, ar, rs, k0, kend, full);       \
+    else acc = dg8_chunk<NORM, 2>(acc, WQ, WN, p, wr, ar, rs, k0, kend, full);                                    \
+    c = cn;                                                                                                       \
+  }
+  while (c < kend) {                                             // c is wave-uniform: scalar branches
+    DG8_STEP(w0, w1)
+    if (c >= kend) break;
+    DG8_STEP(w1, w0)
+  }
+#undef DG8_STEP
+  // 4 waves -> one 16 x 16 tile, fixed order
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
+  __syncthreads();
+  {
+    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
+    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
+  }
+  __syncthreads();
+  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
+  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order, unscaled), summed by the combine kernel
+    const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+    const int nn = dg_row(p, t, nl);
+    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
+    return;
+  }
+  if (swiglu) {
+    if (threadIdx.x < 128) {
+      const int j = threadIdx.x >> 4, mm = threadIdx.x & 15;
+      if (mm < p.M)
+        dg_store(p, mm, 8 * t + j, tile_s[j][mm] * q.wscale[dg_row(p, t, j)], tile_s[j + 8][mm] * q.wscale[dg_row(p, t, j + 8)]);
+    }
+    return;
+  }
+  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm] * q.wscale[16 * t + nl], 0.f);
+}
+
+// sums the KS slabs in order, scales by the row's weight scale and applies the epilogue; one thread per output element
+__global__ __launch_bounds__(256) void decode_gemm_w8_combine_kernel(DecGemmW8Args q) {
+  const DecGemmArgs& p = q.g;
+  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
+  const int nout = swiglu ? p.N / 2 : p.N;
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)p.M * nout) return;
+  const int m = (int)(i / nout), n = (int)(i % nout);
+  const long slab = (long)p.M * p.N;
+  if (swiglu) {
+    const int t = n >> 3, j = n & 7;
+    const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
+    float v = 0.f, u = 0.f;
+    for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
+    dg_store(p, m, n, v * q.wscale[rg], u * q.wscale[ru]);
+    return;
+  }
+  float v = 0.f;
+  for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
+  dg_store(p, m, n, v * q.wscale[n], 0.f);
 }
 
 // ---------------------------------------------------------------- RoPE + KV append ---------------
@@ -390,6 +626,56 @@ int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, 
     hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
   }
   return vp_check_launch("vp_decode_gemm");
+}
+
+int vp_quant_rows_e4m3(int N, int K, void* W, long ldw, void* Q, long ldq, float* scale, int writeback, hipStream_t stream) {
+  VP_REQUIRE(W && Q && scale, VP_ERR_BAD_ARG, "vp_quant_rows_e4m3: null W / Q / scale");
+  VP_REQUIRE(N > 0 && K > 0 && ldw >= K && ldq >= K, VP_ERR_BAD_ARG, "vp_quant_rows_e4m3: N = %d, K = %d, ldw = %ld, ldq = %ld (ld >= K)", N, K,
+             ldw, ldq);
+  VP_REQUIRE(K % 8 == 0 && ldw % 8 == 0 && ldq % 8 == 0 && (((uintptr_t)W) & 15) == 0 && (((uintptr_t)Q) & 7) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_quant_rows_e4m3: K, ldw, ldq must be multiples of 8 (K = %d), W 16-byte and Q 8-byte aligned", K);
+  hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3((unsigned)N), dim3(256), 0, stream, (bf16_t*)W, ldw, (uint8_t*)Q, ldq, scale, K,
+                     writeback ? 1 : 0);
+  return vp_check_launch("vp_quant_rows_e4m3");
+}
+
+long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const int ks = dg8_ksplit(N, K, epilogue);
+  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
+}
+
+int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
+                      const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                      hipStream_t stream) {
+  VP_REQUIRE(A && W && C && w_scale, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: null A / W / w_scale / C");
+  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w8: M = %d (1 <= M <= 16)", M);
+  VP_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && lda % 8 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm_w8: N = %d, K = %d, lda = %ld, ldw = %ld (K, ldw multiples of 16, lda of 8, lda / ldw >= K)", N, K, lda, ldw);
+  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm_w8: A, W and norm_w must be 16-byte aligned");
+  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
+  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
+             epilogue);
+  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm_w8: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
+  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm_w8: residual epilogue writes bf16 only");
+  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm_w8: ldc / ldr too small");
+  const int ks = dg8_ksplit(N, K, epilogue);
+  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: this shape splits K %d ways and needs "
+             "vp_decode_gemm_w8_workspace_bytes() of workspace (got NULL)", ks);
+  DecGemmW8Args p{{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
+                   M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps}, w_scale};
+  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
+  if (norm_w)
+    hipLaunchKernelGGL(decode_gemm_w8_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  else
+    hipLaunchKernelGGL(decode_gemm_w8_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  if (ks > 1) {
+    const long nout = (long)M * (swiglu ? N / 2 : N);
+    hipLaunchKernelGGL(decode_gemm_w8_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
+  }
+  return vp_check_launch("vp_decode_gemm_w8");
 }
 
 int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,

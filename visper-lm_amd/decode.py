@@ -8,7 +8,9 @@ IFT classes — the multimodal splice, then HF's generation loop over `inputs_em
 
 Every per-token scalar (token ids, positions, cache lengths) lives on the device, so one step can be captured once into a CUDA graph
 (single stream, no fork) and replayed for every token (VP_DECODE_GRAPH=1; the default is eager launches: capture did not pay, see below).  Decode reads the same kernel-ready weights
-_decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current."""
+_decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current.
+After Engine.quantize_decoder() the step streams those matrices as e4m3fn bytes instead (vp_decode_gemm_w8; quant.py: the contract); the
+prefill stays on the bf16 weights, which by then hold exactly the dequantised values."""
 from __future__ import annotations
 
 import os
@@ -91,6 +93,9 @@ class DecodeSession:
         # replayed vs 9.06 eager, 3.3 ms of host enqueue under it), so eager launches are the default; VP_DECODE_GRAPH=1 captures
         self.use_graph = os.environ.get("VP_DECODE_GRAPH", "0") == "1"
         self.replays = 0
+        # FP8 weight-only decoding (Engine.quantize_decoder): {fz key: (e4m3fn bytes, per-row scales)} of the matrices the step streams as fp8,
+        # or None (bf16).  Read once per session: a session never mixes the two, and stale copies were already dropped by fp8_weights().
+        self.fq = eng.fp8_weights()
 
     # ---------------------------------------------------------------------------------------------- prefill
     def prefill(self, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=16):
@@ -140,12 +145,19 @@ class DecodeSession:
         self.logits = e(B, V, dt=torch.float32)
         self.epi = ops.EPI_SWIGLU_IL if eng.gu_interleaved else ops.EPI_SWIGLU_HALVES
         shapes = [(nqkv, H, 0), (H, nh * hd, 0), (2 * I, H, self.epi), (H, I, 0), (V, H, 0)]
-        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep) for N, K, ep in shapes)
+        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep, w8) for N, K, ep in shapes for w8 in ((False, True) if self.fq else (False,)))
         self.gws = e(max(1, nb // 4), dt=torch.float32) if nb > 0 else None
         Smax = self.cache.Smax
         self.nsplit = ops.decode_attn_splits(B, nkv, Smax)
         self.aws = e(ops._lib.raw("vp_decode_attn_workspace_bytes", B, nh, nkv, hd, self.nsplit) // 4, dt=torch.float32)
         self.cos, self.sin = eng.rope(max(Smax, 1))
+
+    def _gemm(self, a, key, **kw):
+        """One skinny GEMM of the step on weight `key`: its fp8 copy when the session decodes from fp8 weights, else the bf16 weight."""
+        q = self.fq.get(key) if self.fq else None
+        if q is None:
+            return ops.decode_gemm(a, self.eng.fz[key], **kw)
+        return ops.decode_gemm(a, q[0], w_scale=q[1], **kw)
 
     def _step_launches(self):
         """The per-token launches (everything they read or write is preallocated: graph-capturable)."""
@@ -157,15 +169,15 @@ class DecodeSession:
         ops.gather_rows([fz["embed"]], self.zeros_b, self.tok, H, x)
         for l in range(cfg.num_hidden_layers):
             o = f"dec.{l}."
-            ops.decode_gemm(x, fz[o + "wqkv"], norm_w=fz[o + "ln1"], eps=eps, out=self.qkv, ws=self.gws)
+            self._gemm(x, o + "wqkv", norm_w=fz[o + "ln1"], eps=eps, out=self.qkv, ws=self.gws)
             ops.decode_rope_append(self.qkv, self.q, c.k(l), c.v(l), self.cos, self.sin, c.pos, nh, nkv, hd)
             ops.decode_attn(self.q, c.k(l), c.v(l), c.kv_len, nh, window=window, nsplit=self.nsplit, out=self.att, ws=self.aws)
-            ops.decode_gemm(self.att, fz[o + "wo"], residual=x, out=self.h1, ws=self.gws)
-            ops.decode_gemm(self.h1, fz[o + "wgu"], norm_w=fz[o + "ln2"], eps=eps, epi=self.epi, out=self.act, ws=self.gws)
+            self._gemm(self.att, o + "wo", residual=x, out=self.h1, ws=self.gws)
+            self._gemm(self.h1, o + "wgu", norm_w=fz[o + "ln2"], eps=eps, epi=self.epi, out=self.act, ws=self.gws)
             xn = self.x[(l + 1) % 2]
-            ops.decode_gemm(self.act, fz[o + "wd"], residual=self.h1, out=xn, ws=self.gws)
+            self._gemm(self.act, o + "wd", residual=self.h1, out=xn, ws=self.gws)
             x = xn
-        ops.decode_gemm(x, fz["lm_head"], norm_w=fz["norm"], eps=eps, out_f32=True, out=self.logits, ws=self.gws)
+        self._gemm(x, "lm_head", norm_w=fz["norm"], eps=eps, out_f32=True, out=self.logits, ws=self.gws)
         ops.add_i32_(c.lens, 1)
 
     def step(self, tokens):

@@ -173,6 +173,7 @@ class Engine:
         self.lm_chunk_rows = lm_chunk_rows
         self.rank, self.world = 0, 1
         self.fz = {}           # frozen, kernel-ready weights
+        self.fq = None         # fp8 copies of the decoder matrices (quantize_decoder), or None
         self.ps = None         # ParamStore
         self._rope = {}
         self._plan_cache = {}          # per-batch splice plans (small LRU-ish cache: identical batches reuse their tables)
@@ -235,6 +236,7 @@ class Engine:
         cfg, dev = self.cfg, self.dev
         d = lambda t: t.detach().to(device=dev, dtype=BF16).contiguous()
         fz = self.fz = {}
+        self.fq = None                                           # fp8 copies (quantize_decoder) belong to the weights they were made from
         # ---- CLIP tower (both transformers naming generations: with / without ".vision_model")
         vp = "model.vision_tower.vision_tower.vision_model."
         if vp + "embeddings.class_embedding" not in W:
@@ -397,6 +399,52 @@ class Engine:
             o = f"dec.{l}."
             for k in ("wqkv", "wgu", "wo", "wd"):
                 ops.transpose(fz[o + k], out=fz[o + k + "_T"])
+
+    # ------------------------------------------------------------------------------------------ FP8 weight-only decode
+    def quantize_decoder(self, lm_head=False):
+        """FP8 weight-only decoding for generate() (quant.py: the contract; stands in for the reference's load_8bit, builder.py:26-34).  Every
+        decoder matrix the decode step reads (per layer wqkv, wo, wgu, wd; lm_head when asked) is quantised to e4m3fn bytes with per-row
+        power-of-two scales, WITH write-back: the engine's bf16 weights become the dequantised model (exact), so prefill, the training forward
+        and logits_of see the weights the decode step streams as fp8.  The bf16 copy stays (prefill needs it).  The fp8 copies live in
+        `self.fq` beside `fz`; DecodeSession uses them while they are current (fp8_weights()).  Calling it again on unchanged weights gives the same model.
+        On an engine whose decoder trains (train_llm) the write-back changes the bf16 shadow only; the fp32 master keeps the un-quantised
+        weights.  state_dict() of a mirror then returns dequantised values for its bf16 Parameters (they alias the shadow), and the next
+        optimizer step rebuilds the shadow from master + update: quantising for an evaluation does not damage the training run, it is
+        undone by the next step (and the fp8 copies are dropped then, fp8_weights()).  On a frozen decoder the write-back is permanent
+        until load_weights."""
+        fz = self.fz
+        keys = [f"dec.{l}.{k}" for l in range(self.cfg.num_hidden_layers) for k in ("wqkv", "wo", "wgu", "wd")] + (["lm_head"] if lm_head else [])
+        fq = {}
+        for k in keys:
+            fq[k] = ops.quant_rows_e4m3(fz[k], writeback=True)
+        if getattr(self, "train_llm", False):
+            self.ps.version += 1                                 # the shadow changed under the derived caches
+        self.refresh_transposes()                                # the dgrad copies follow the written-back weights
+        self.fq = fq
+        self._fq_version = self.ps.version if self.ps is not None else None
+        self._fq_warned = False
+        return self
+
+    def fp8_weights(self):
+        """{fz key: (q uint8 [N, K], scale fp32 [N])} while the fp8 copies match the bf16 weights, else None.  On an engine whose decoder
+        trains, any change of the parameter store after quantize_decoder (optimizer step, load, in-place edit folded in by _sync_trainable)
+        makes them stale: they are dropped, with one warning, and decoding goes through the bf16 kernels."""
+        fq = self.fq
+        if fq is None:
+            return None
+        if getattr(self, "train_llm", False) and self.ps.version != self._fq_version:
+            self.fq = None
+            if not self._fq_warned:
+                self._fq_warned = True
+                import warnings
+                warnings.warn("decoder weights changed after quantize_decoder(): the fp8 copies are stale and were dropped; generate() decodes "
+                              "through the bf16 kernels (call quantize_for_generation() again to re-quantise)", RuntimeWarning, stacklevel=2)
+            return None
+        return fq
+
+    def dequantized(self):
+        """True while generate() decodes from fp8 weights (and the bf16 weights are their dequantised values)."""
+        return self.fp8_weights() is not None
 
     def _gfused(self, key):
         """fp32 gradient view of a fused weight (same layout as the fused bf16 view)."""

@@ -402,6 +402,18 @@ class EngineModule(nn.Module):
         self._sync_trainable()                                   # fold in external edits first (they would be overwritten otherwise)
         self._get_engine().optimizer_step(lr, **kw)
 
+    def quantize_for_generation(self, lm_head=False):
+        """FP8 weight-only decoding for generate(): what the reference reaches with load_pretrained_model(..., load_8bit=True) through
+        bitsandbytes (ola_vlm/model/builder.py:26-34), here OCP e4m3fn decoder weights with per-row power-of-two scales
+        (Engine.quantize_decoder; quant.py documents the contract).  The engine's bf16 decoder weights become the dequantised model, so
+        forward(), prefill and generate() agree on the weights; `lm_head=True` quantises the output projection as well.  generate() keeps
+        its signature and refusals.  If the decoder is trained afterwards the fp8 copies are dropped (one warning) and decoding is bf16
+        again.  Returns self."""
+        with torch.no_grad():
+            self._sync_trainable()                               # external edits first: the copies are made from current weights
+            self._get_engine().quantize_decoder(lm_head=lm_head)
+        return self
+
     def reload_frozen(self):
         """Call after load_state_dict(): rebuilds the engine's fused / pre-transposed frozen weights."""
         self._engine = None
