@@ -239,6 +239,24 @@ long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue);
 int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       vp_stream_t stream);
+/* MXFP4 weight-only decoding: the 4-bit half of the same loading options (load_4bit), on gfx950 as OCP MXFP4: e2m1 codes (0, 0.5, 1, 1.5, 2, 3, 4,
+ * 6; bit 3 = sign), two per byte (element k in byte k / 2, even k in the low nibble), row-major, and one e8m0 scale byte (2^(byte - 127)) per
+ * block of 32 consecutive k of a row.  K % 32 == 0.
+ * vp_quant_blocks_mxfp4: W bf16 [N, K] (finite) -> Q uint8 [N, K/2] codes + E uint8 [N, K/32] scale bytes.  Per block: the smallest power of two
+ *   with absmax / s <= 6 (exponent clamped below at -120, so every nonzero dequantised value is a normal bf16 number; a block of zeros: byte
+ *   127), Q = e2m1(W / s) rounded to nearest, ties to the even code, the weight's sign bit kept also on a zero; nothing saturates.
+ *   writeback != 0: W is overwritten in place with bf16(Q * s), which is exact (the bf16 kernels on the written-back weights and
+ *   vp_decode_gemm_w4 on Q, E then compute the same model).  ldw in elements (a multiple of 8), ldq and lde in bytes (ldq a multiple of 16),
+ *   W and Q 16-byte aligned.
+ * vp_decode_gemm_w4: vp_decode_gemm with W = uint8 [N, K/2] codes and E = uint8 [N, K/32] scale bytes (ldw and lde in bytes): a 16-byte load
+ *   carries one scale block; the codes are converted to bf16 in registers with the block scale applied by the conversion itself (exact) and
+ *   fed to the same MFMA against the bf16 activation (A is not quantised), so the epilogue has no scale multiply.  Same prologue, epilogues,
+ *   split-K contract (its own vp_decode_gemm_w4_workspace_bytes) and error codes as vp_decode_gemm; K a multiple of 32, ldw of 16. */
+int vp_quant_blocks_mxfp4(int N, int K, void* W, long ldw, void* Q, long ldq, void* E, long lde, int writeback, vp_stream_t stream);
+long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C, long ldc,
+                      const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                      vp_stream_t stream);
 /* RoPE of the new token and the KV append (HF apply_rotary_pos_emb + DynamicCache.update, modeling_llama.py, at position pos[b] of each
  * sequence): qkv [B, ldqkv] rows (Hq q heads | Hkv k heads | Hkv v heads, head_dim D); q rotated into q_out [B, ldq]; k rotated and v copied
  * into row pos[b] of the caches ([B, Smax, Hkv, D] views, strides in elements).  cos_t / sin_t: fp32 [>= Smax, D/2] (ops.rope_tables); pos:

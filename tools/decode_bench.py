@@ -12,6 +12,13 @@ times each, in this one process on the same engine and prompts; the JSON carries
 bf16 leg and the ratio.  A gain counts only where the fp8 median is below the bf16 median by more than that spread.
 
   python tools/decode_bench.py --model llama3 --weights fp8 --out profiles/decode_bench_llama3_fp8.json
+
+--weights mxfp4: one engine, quantised to MXFP4 with write-back (Engine.quantize_decoder(fmt="mxfp4")); e4m3 copies of the same written-back
+weights are made beside them without a second write-back (only their time matters).  Three legs alternate, --repeats runs each, in one
+process: the bf16 kernels on the written-back weights, the fp8 leg, the mxfp4 leg.  A cell is a "gain" only if the slowest mxfp4 run lies
+below the fastest fp8 run.
+
+  python tools/decode_bench.py --model llama3 --weights mxfp4 --out profiles/decode_bench_llama3_mxfp4.json
 """
 import argparse
 import json
@@ -101,6 +108,32 @@ def fp8_legs(eng, B, new, text_tokens, repeats, use_graph):
                 gain_exceeds_bf16_spread=bool(med(tb) - med(t8) > spread), runs=legs["bf16"] + legs["fp8"])
 
 
+def mxfp4_legs(eng, fq8, B, new, text_tokens, repeats, use_graph):
+    """bf16, fp8 and mxfp4 legs alternately on the engine quantised to mxfp4 -> dict with every run, the medians and the verdict"""
+    fq4 = eng.fq
+    assert fq4 is not None and eng.fq_format == "mxfp4"
+    copies = {"bf16": (None, None), "fp8": (fq8, "e4m3"), "mxfp4": (fq4, "mxfp4")}
+    legs = {k: [] for k in copies}
+    for _ in range(repeats):
+        for leg, (fq, fmt) in copies.items():
+            eng.fq, eng.fq_format = fq, fmt
+            try:
+                r = time_decode(eng, B, new, text_tokens, use_graph)
+            finally:
+                eng.fq, eng.fq_format = fq4, "mxfp4"
+            r["weights"] = leg
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    t = {k: [r["ms_per_token"] for r in v] for k, v in legs.items()}
+    gain = max(t["mxfp4"]) < min(t["fp8"])
+    return dict(B=B, graph=use_graph, repeats=repeats, bf16_ms_per_token=t["bf16"], fp8_ms_per_token=t["fp8"], mxfp4_ms_per_token=t["mxfp4"],
+                bf16_median=med(t["bf16"]), fp8_median=med(t["fp8"]), mxfp4_median=med(t["mxfp4"]),
+                mxfp4_over_fp8=round(med(t["mxfp4"]) / med(t["fp8"]), 4), mxfp4_over_bf16=round(med(t["mxfp4"]) / med(t["bf16"]), 4),
+                slowest_mxfp4=max(t["mxfp4"]), fastest_fp8=min(t["fp8"]), verdict="gain" if gain else "no gain",
+                runs=legs["bf16"] + legs["fp8"] + legs["mxfp4"])
+
+
 def weight_bytes(eng):
     cfg = eng.cfg
     H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
@@ -117,9 +150,10 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--profile", action="store_true", help="graph on only (for a rocprofv3 --kernel-trace --stats run)")
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8"], help="fp8: bf16 leg, then fp8 leg, on the same quantised engine")
-    ap.add_argument("--repeats", type=int, default=3, help="--weights fp8: runs of each leg, alternating")
-    ap.add_argument("--graph", action="store_true", help="--weights fp8: time the captured step instead of eager launches")
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="fp8: bf16 leg, then fp8 leg, on the same quantised engine; mxfp4: bf16, fp8 and mxfp4 legs on the engine quantised to mxfp4")
+    ap.add_argument("--repeats", type=int, default=3, help="--weights fp8 / mxfp4: runs of each leg, alternating")
+    ap.add_argument("--graph", action="store_true", help="--weights fp8 / mxfp4: time the captured step instead of eager launches")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
@@ -142,7 +176,24 @@ def main():
             cell["bf16_weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 8e12 * 1e3 / cell["bf16_median"], 3)
             res["runs"] += cell.pop("runs")
             res["cells"].append(cell)
-    for B in ([] if a.weights == "fp8" else [int(x) for x in a.batches.split(",")]):
+    if a.weights == "mxfp4":
+        from visper_lm_amd import ops
+        eng.quantize_decoder(lm_head=True, fmt="mxfp4")
+        fq8 = {k: ops.quant_rows_e4m3(eng.fz[k]) for k in eng.fq}            # e4m3 copies of the written-back weights, no second write-back
+        # mxfp4 bytes per weight: half a byte of codes + one scale byte per 32
+        res.update(weights="mxfp4", lm_head_mxfp4=True, mxfp4_roofline_ms_per_token_8tbps=round((dec_b + head_b) / 2 * (0.5 + 1 / 32) / 8e12 * 1e3, 3),
+                   cells=[])
+        for B in [int(x) for x in a.batches.split(",")]:
+            if a.profile:                                         # kernel-trace run: the mxfp4 leg alone, captured step
+                r = time_decode(eng, B, a.new, a.text, True)
+                r["weights"] = "mxfp4"
+                res["runs"].append(r)
+                print(json.dumps(r), flush=True)
+                continue
+            cell = mxfp4_legs(eng, fq8, B, a.new, a.text, a.repeats, a.graph)
+            res["runs"] += cell.pop("runs")
+            res["cells"].append(cell)
+    for B in ([] if a.weights != "bf16" else [int(x) for x in a.batches.split(",")]):
         for g in ((True,) if a.profile else (True, False)):
             r = time_decode(eng, B, a.new, a.text, g)
             kv_bytes_per_pos = 2 * 2 * eng.cfg.num_key_value_heads * eng.cfg.head_dim * eng.cfg.num_hidden_layers

@@ -23,10 +23,11 @@ def shapes(model):
                  ("down", H, I, False), ("lm_head", cfg.vocab_size, H, False)]
 
 
-def ksplit_w8(N, K, swiglu):
-    """(tiles, split-K factor) of decode_gemm_w8_kernel, asked of the library itself: the workspace is ks fp32 slabs [M, N] (none: ks = 1)"""
+def ksplit_w8(N, K, swiglu, query="vp_decode_gemm_w8_workspace_bytes"):
+    """(tiles, split-K factor) of decode_gemm_w8_kernel (decode_gemm_w4_kernel with its own query), asked of the library itself: the
+    workspace is ks fp32 slabs [M, N] (none: ks = 1)"""
     from visper_lm_amd import _lib
-    nb = int(_lib.raw("vp_decode_gemm_w8_workspace_bytes", 1, N, K, 4 if swiglu else 0))
+    nb = int(_lib.raw(query, 1, N, K, 4 if swiglu else 0))
     # M = 1: ks = bytes / (4 N).  This holds only while the workspace is EXACTLY ks slabs of M x N fp32 (include/visper_hip.h); a header, padding
     # or a different slab type in the library would make the rows below attach to the wrong grid (they would then simply find no match)
     assert nb % (4 * N) == 0, (N, K, nb)
@@ -56,6 +57,10 @@ def main():
     for name, N, K, sw in shp:
         tiles, ks = ksplit_w8(N, K, sw)
         by_grid8.setdefault((tiles * 256, ks), []).append((name, N, K))
+    by_grid4 = {}                                                 # the MXFP4 weight-only kernel: half a byte per weight + a scale byte per 32
+    for name, N, K, sw in shp:
+        tiles, ks = ksplit_w8(N, K, sw, "vp_decode_gemm_w4_workspace_bytes")
+        by_grid4.setdefault((tiles * 256, ks), []).append((name, N, K))
     c = sqlite3.connect(a.db)
     rows = c.execute("select name, grid_x, grid_y, grid_z, duration from kernels").fetchall()
     agg = {}
@@ -79,6 +84,11 @@ def main():
             grp = by_grid8[(gx, gy)]
             nbytes = sum(N * K for _, N, K in grp) // len(grp)
             shape = " + ".join(f"{nm} N={N} K={K}" for nm, N, K in grp) + f" (fp8, split-K {gy})"
+            gbps_share = round(nbytes / (avg_us * 1e-6) / 8e12, 3)
+        if "decode_gemm_w4_kernel" in short and (gx, gy) in by_grid4:
+            grp = by_grid4[(gx, gy)]
+            nbytes = sum(N * K // 2 + N * K // 32 for _, N, K in grp) // len(grp)
+            shape = " + ".join(f"{nm} N={N} K={K}" for nm, N, K in grp) + f" (mxfp4, split-K {gy})"
             gbps_share = round(nbytes / (avg_us * 1e-6) / 8e12, 3)
         out.append(dict(kernel=short, grid=f"{gx}x{gy}x{gz}", calls=n, total_ms=round(t / 1e6, 3), avg_us=round(avg_us, 2), shape=shape,
                         weight_bytes=nbytes, share_of_8TBps=gbps_share))

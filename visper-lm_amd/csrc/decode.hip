@@ -12,6 +12,7 @@
 //    K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
 #include "common.h"
 #include "fp8_e4m3.h"
+#include "mxfp4.h"
 
 #define VP_EPI_NONE 0
 #define VP_EPI_SWIGLU_IL 4      // SwiGLU on the interleaved gate|up rows (8 gate rows, 8 up rows, ...)
@@ -404,6 +405,263 @@ __global__ __launch_bounds__(256) void decode_gemm_w8_combine_kernel(DecGemmW8Ar
   dg_store(p, m, n, v * q.wscale[n], 0.f);
 }
 
+// ---------------------------------------------------------------- MXFP4 weight-only decode ---------------
+// The 4-bit half of the same loading options (load_4bit): OCP MXFP4 (mxfp4.h, quant.py: the contract), e2m1 codes in blocks of 32 k with one
+// e8m0 scale byte per block.  gfx950 converts a pair of codes to a bf16 pair with the block scale applied by the conversion
+// (v_cvt_scalef32_pk_bf16_fp4, exact: a 2-bit significand times a power of two), so a 16-byte load carries 32 weights = one scale block.
+//  - quant_blocks_mxfp4_kernel: one thread per block of 32 k: absmax -> scale byte -> 16 bytes of codes (+ the dequantised value written back
+//    over the bf16 block), integer arithmetic only.
+//  - decode_gemm_w4_kernel: decode_gemm_w8_kernel's structure (one 16-row W tile per block, K over the 4 waves and KS blocks, the same MFMA
+//    with the same k permutation on both operands, dg_norm / dg_store); a wave consumes 512 k per chunk = 4 loads of 32 codes per lane, each
+//    feeding four MFMAs.  The chunk's 16 scale bytes of a row come in one 16-byte load per lane, issued with the weight loads (lane group g
+//    uses byte g of word u for load u), so no weight load waits for a scale.  The next chunk's loads are issued before the current chunk is
+//    converted, the first chunk's before the rstd pass.  The scale is part of the converted value: the epilogue has no per-row multiply.
+__global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(bf16_t* __restrict__ W, long ldw, uint8_t* __restrict__ Q, long ldq,
+                                                                 uint8_t* __restrict__ E, long lde, int N, int K, int writeback) {
+  const int nb = K / VP_MXFP4_BLOCK;
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)N * nb) return;
+  const long n = i / nb;
+  const int b = (int)(i % nb);
+  bf16_t* wb = W + n * ldw + b * VP_MXFP4_BLOCK;
+  bf16x8 v[4];
+  uint32_t am = 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    v[u] = *(const bf16x8*)(wb + u * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[u][j] & 0x7fffu);
+  }
+  const int se = vp_mxfp4_scale_exp(am);
+  E[n * lde + b] = (uint8_t)(se + 127);
+  u32x4 qv;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    uint32_t word = 0;
+    bf16x8 d;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t c = vp_mxfp4_quant((uint16_t)v[u][j], se);
+      word |= c << (4 * j);                                       // element k in byte k / 2, even k in the low nibble
+      d[j] = (short)vp_mxfp4_dequant_bf16(c, se);
+    }
+    qv[u] = word;
+    if (writeback) *(bf16x8*)(wb + u * 8) = d;
+  }
+  *(u32x4*)(Q + n * ldq + b * 16) = qv;
+}
+
+static constexpr int DG4_KCHUNK = 512;       // K elements one wave consumes per iteration: 4 loads x 4 lane groups x 32 codes (16 scale blocks)
+static constexpr int DG4_LOADS = 4;
+
+struct DecGemmW4Args {
+  DecGemmArgs g;                             // g.W = the packed codes, g.ldw in bytes
+  const uint8_t* E;                          // e8m0 scale bytes [N, K / 32]
+  long lde;
+};
+
+// a 512-k chunk per wave (not 1024) leaves K = 4096 two chunk rounds of the 4 waves, so split-K can still halve it
+static int dg4_ksplit(int N, int K, int epi) {
+  const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
+  int ks = 1;
+  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG4_KCHUNK) == 0) ks *= 2;
+  return ks;
+}
+
+// 8 e2m1 codes (one 32-bit word: k .. k + 7) times the block scale -> one MFMA fragment, exact.  One instruction per two weights; its last
+// operand selects the byte of the word
+__device__ __forceinline__ bf16x8 dg4_cvt(uint32_t word, float scale) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  u32x4 a;
+  a[0] = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 0));
+  a[1] = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 1));
+  a[2] = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 2));
+  a[3] = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 3));
+  return __builtin_bit_cast(bf16x8, a);
+}
+
+// loads u0 .. u0 + L - 1 of one lane's 4 loads of a chunk (32 k = 16 bytes each, 128 k apart: the 4 lane groups of a row read 64 consecutive
+// bytes per load instruction, as in the W8 kernel).  Past kend (K and Kc are multiples of 32) a load re-reads the range's last block and its
+// value becomes zero (code 0 times any scale is 0): no load is conditional, every address lies inside the row.
+template <int L>
+__device__ __forceinline__ void dg4_load(u32x4* wq, const uint8_t* wr, int k0, int kend, bool full) {
+  if (full) {
+#pragma unroll
+    for (int u = 0; u < L; ++u) wq[u] = __builtin_nontemporal_load((const u32x4*)(wr + ((k0 + u * 128) >> 1)));
+  } else {
+#pragma unroll
+    for (int u = 0; u < L; ++u) {
+      const bool ok = k0 + u * 128 < kend;
+      const u32x4 v = __builtin_nontemporal_load((const u32x4*)(wr + ((ok ? k0 + u * 128 : kend - 32) >> 1)));
+      wq[u] = v & (ok ? ~0u : 0u);
+    }
+  }
+}
+
+// the scale bytes of one lane's 4 loads of the chunk at c.  vec (a whole chunk, the row's scale bytes 16-byte aligned): the chunk's run of 16
+// bytes in one load, load u's byte is byte g of word u; otherwise 4 byte loads (index clamped into the K range), the byte is word u itself
+__device__ __forceinline__ u32x4 dg4_load_scales(const uint8_t* er, int c, int g, int kend, bool vec) {
+  if (vec) return *(const u32x4*)(er + (c >> 5));
+  u32x4 s;
+#pragma unroll
+  for (int u = 0; u < DG4_LOADS; ++u) s[u] = er[min(c + g * 32 + u * 128, kend - 32) >> 5];
+  return s;
+}
+
+// One lane's share of a chunk: 16 MFMAs on the 4 converted loads of wq, in parts of L loads (2; 1 with the norm prologue, whose gamma
+// vectors need the registers).  Each part issues its 4 L A fragments (bf16, L2-resident; + gamma) FIRST and then L loads of the next chunk
+// (wn; part 0 also its scale bytes, sn), so waiting for A leaves those W loads in flight under the conversion.  Past kend A re-reads valid
+// elements (clamped address) against zero weights.  NEXT: 0 = no next chunk, 1 = a whole one, 2 = a partial one.
+template <bool NORM, int NEXT>
+__device__ __forceinline__ f32x4 dg4_chunk(f32x4 acc, const u32x4* wq, const u32x4 sq, int ssh, u32x4* wn, u32x4& sn, const DecGemmArgs& p,
+                                           const uint8_t* wr, const uint8_t* er, const bf16_t* ar, float rs, int c, int g, int kend,
+                                           bool full, bool evec) {
+  constexpr int L = NORM ? 1 : 2;
+  const int k0 = c + g * 32;
+#pragma unroll
+  for (int h = 0; h < DG4_LOADS / L; ++h) {
+    bf16x8 av[4 * L], gv[4 * L];
+#pragma unroll
+    for (int u = 0; u < 4 * L; ++u) {
+      int k = k0 + (h * L + (u >> 2)) * 128 + (u & 3) * 8;         // the four quarters of load h * L + u / 4
+      if (!full) k = min(k, kend - 8);
+      av[u] = *(const bf16x8*)(ar + k);
+      if (NORM) gv[u] = *(const bf16x8*)(p.gamma + k);
+    }
+    if (NEXT) {
+      if (h == 0) sn = dg4_load_scales(er, c + 4 * DG4_KCHUNK, g, kend, NEXT == 1 && evec);
+      dg4_load<L>(wn + L * h, wr, k0 + 4 * DG4_KCHUNK + h * L * 128, kend, NEXT == 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);                           // the loads above stay above: no conversion is hoisted over them (registers)
+#pragma unroll
+    for (int u = 0; u < L; ++u) {
+      if (NORM) {
+#pragma unroll
+        for (int v = 4 * u; v < 4 * u + 4; ++v) av[v] = dg_norm(av[v], (const bf16_t*)&gv[v], rs);
+      }
+      u32x4 wv = wq[h * L + u];
+      asm volatile("" : "+v"(wv));                                 // pins the conversion below the loads of its own part
+      // 2^(byte - 127) as fp32 bits: byte << 23 (byte >= 7: a normal number)
+      const float sc = __builtin_bit_cast(float, ((sq[h * L + u] >> ssh) & 0xffu) << 23);
+      // D[n][m] += sum_k W[n][k] A[m][k]: both operands carry the same k permutation (lane group g owns 32 k of every 128 of the chunk)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dg4_cvt(wv[f], sc), av[4 * u + f], acc, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return acc;
+}
+
+// rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical); wave w takes
+// rows w, w + 4, ...; ends with the block's barrier
+__device__ __forceinline__ void dg_rstd_rows(const DecGemmArgs& p, int w, int lane, float* rstd_s) {
+  for (int mm = w; mm < p.M; mm += 4) {
+    const bf16_t* a2 = p.A + (long)mm * p.lda;
+    float ss = 0.f;
+    for (int e = lane * 8; e < p.K; e += 512) {
+      const bf16x8 v = *(const bf16x8*)(a2 + e);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) rstd_s[mm] = rsqrtf(ss / (float)p.K + p.eps);
+  }
+  __syncthreads();
+}
+
+// the 4 waves' accumulators -> one 16 x 16 tile in a fixed order, then the fp32 slab of split ks (KS > 1) or the epilogue (no row scale)
+__device__ __forceinline__ void dg_reduce_store(const DecGemmArgs& p, f32x4 acc, int t, int ks, int w, int lane, float (*red)[256],
+                                                float (*tile_s)[17]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
+  __syncthreads();
+  {
+    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
+    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
+  }
+  __syncthreads();
+  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
+    const int nn = dg_row(p, t, nl);
+    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
+    return;
+  }
+  if (p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES) {
+    if (threadIdx.x < 128 && mm < p.M) dg_store(p, mm, 8 * t + nl, tile_s[nl][mm], tile_s[nl + 8][mm]);
+    return;
+  }
+  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm], 0.f);
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmW4Args q) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16];
+  const DecGemmArgs& p = q.g;
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  // rows past N / M are clamped to the last valid row: their results are never stored, so the hot loop needs no masks
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const int m = min(r, p.M - 1);
+  const uint8_t* wr = (const uint8_t*)p.W + (long)n * p.ldw;
+  const uint8_t* er = q.E + (long)n * q.lde;
+  const bf16_t* ar = p.A + (long)m * p.lda;
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  // every row's scale bytes 16-byte aligned (block-uniform): whole chunks fetch their 16 scale bytes in one load
+  const bool evec = ((((uintptr_t)q.E) | (uintptr_t)q.lde) & 15) == 0;
+  int c = kbeg + w * DG4_KCHUNK;
+  u32x4 w0[DG4_LOADS], w1[DG4_LOADS], s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};  // ping-pong: one chunk converts while the next one streams
+  if (c < kend) {                                                // the first chunk is in flight under the rstd pass
+    s0 = dg4_load_scales(er, c, g, kend, evec && c + DG4_KCHUNK <= kend);
+    dg4_load<DG4_LOADS>(w0, wr, c + g * 32, kend, c + DG4_KCHUNK <= kend);
+  }
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
+  const float rs = NORM ? rstd_s[m] : 1.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  // ssh: which byte of a scale word belongs to this lane: byte g of the 16-byte run, the whole word after byte loads
+#define DG4_STEP(WQ, SQ, WN, SN)                                                                                           \
+  {                                                                                                                        \
+    const int cn = c + 4 * DG4_KCHUNK;                                                                                     \
+    const bool full = c + DG4_KCHUNK <= kend;                                                                              \
+    const int ssh = (full && evec) ? 8 * g : 0;                                                                            \
+    if (cn >= kend) acc = dg4_chunk<NORM, 0>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, ar, rs, c, g, kend, full, evec);         \
+    else if (cn + DG4_KCHUNK <= kend) acc = dg4_chunk<NORM, 1>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, ar, rs, c, g, kend, full, evec); \
+    else acc = dg4_chunk<NORM, 2>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, ar, rs, c, g, kend, full, evec);                    \
+    c = cn;                                                                                                                \
+  }
+  while (c < kend) {                                             // c is wave-uniform: scalar branches
+    DG4_STEP(w0, s0, w1, s1)
+    if (c >= kend) break;
+    DG4_STEP(w1, s1, w0, s0)
+  }
+#undef DG4_STEP
+  dg_reduce_store(p, acc, t, ks, w, lane, red, tile_s);
+}
+
+// sums the KS slabs in order and applies the epilogue (the scales are already in the sums); one thread per output element
+__global__ __launch_bounds__(256) void decode_gemm_w4_combine_kernel(DecGemmArgs p) {
+  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
+  const int nout = swiglu ? p.N / 2 : p.N;
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)p.M * nout) return;
+  const int m = (int)(i / nout), n = (int)(i % nout);
+  const long slab = (long)p.M * p.N;
+  if (swiglu) {
+    const int t = n >> 3, j = n & 7;
+    const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
+    float v = 0.f, u = 0.f;
+    for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
+    dg_store(p, m, n, v, u);
+    return;
+  }
+  float v = 0.f;
+  for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
+  dg_store(p, m, n, v, 0.f);
+}
+
 // ---------------------------------------------------------------- RoPE + KV append ---------------
 // qkv [B, ldq] rows (q heads | k heads | v heads); thread = one 8-wide vector of one head's first half (q / k) or 16 elements of v
 __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo, long ldq,
@@ -676,6 +934,58 @@ int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* 
     hipLaunchKernelGGL(decode_gemm_w8_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
   }
   return vp_check_launch("vp_decode_gemm_w8");
+}
+
+int vp_quant_blocks_mxfp4(int N, int K, void* W, long ldw, void* Q, long ldq, void* E, long lde, int writeback, hipStream_t stream) {
+  VP_REQUIRE(W && Q && E, VP_ERR_BAD_ARG, "vp_quant_blocks_mxfp4: null W / Q / E");
+  VP_REQUIRE(N > 0 && K > 0 && ldw >= K && ldq >= K / 2 && lde >= K / 32, VP_ERR_BAD_ARG,
+             "vp_quant_blocks_mxfp4: N = %d, K = %d, ldw = %ld, ldq = %ld, lde = %ld (ldw >= K, ldq >= K / 2, lde >= K / 32)", N, K, ldw, ldq, lde);
+  VP_REQUIRE(K % 32 == 0 && ldw % 8 == 0 && ldq % 16 == 0 && ((((uintptr_t)W) | ((uintptr_t)Q)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_quant_blocks_mxfp4: K must be a multiple of 32 (K = %d), ldw of 8, ldq of 16, W and Q 16-byte aligned", K);
+  const long blocks = (long)N * (K / 32);
+  hipLaunchKernelGGL(quant_blocks_mxfp4_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, stream, (bf16_t*)W, ldw, (uint8_t*)Q,
+                     ldq, (uint8_t*)E, lde, N, K, writeback ? 1 : 0);
+  return vp_check_launch("vp_quant_blocks_mxfp4");
+}
+
+long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const int ks = dg4_ksplit(N, K, epilogue);
+  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
+}
+
+int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C, long ldc,
+                      const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                      hipStream_t stream) {
+  VP_REQUIRE(A && W && C && E, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: null A / W / E (block scales) / C");
+  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w4: M = %d (1 <= M <= 16)", M);
+  VP_REQUIRE(N > 0 && K > 0 && K % 32 == 0 && lda % 8 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K / 2 && lde >= K / 32,
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w4: N = %d, K = %d, lda = %ld, ldw = %ld, lde = %ld (K a multiple of 32, ldw (bytes) of 16, "
+             "lda of 8, lda >= K, ldw >= K / 2, lde >= K / 32)", N, K, lda, ldw, lde);
+  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm_w4: A, W and norm_w must be 16-byte aligned");
+  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
+  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
+             epilogue);
+  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_gemm_w4: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
+  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm_w4: residual epilogue writes bf16 only");
+  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm_w4: ldc / ldr too small");
+  const int ks = dg4_ksplit(N, K, epilogue);
+  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: this shape splits K %d ways and needs "
+             "vp_decode_gemm_w4_workspace_bytes() of workspace (got NULL)", ks);
+  DecGemmW4Args p{{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
+                   M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps}, (const uint8_t*)E, lde};
+  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
+  if (norm_w)
+    hipLaunchKernelGGL(decode_gemm_w4_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  else
+    hipLaunchKernelGGL(decode_gemm_w4_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
+  if (ks > 1) {
+    const long nout = (long)M * (swiglu ? N / 2 : N);
+    hipLaunchKernelGGL(decode_gemm_w4_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p.g);
+  }
+  return vp_check_launch("vp_decode_gemm_w4");
 }
 
 int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,

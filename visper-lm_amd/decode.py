@@ -9,8 +9,8 @@ IFT classes — the multimodal splice, then HF's generation loop over `inputs_em
 Every per-token scalar (token ids, positions, cache lengths) lives on the device, so one step can be captured once into a CUDA graph
 (single stream, no fork) and replayed for every token (VP_DECODE_GRAPH=1; the default is eager launches: capture did not pay, see below).  Decode reads the same kernel-ready weights
 _decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current.
-After Engine.quantize_decoder() the step streams those matrices as e4m3fn bytes instead (vp_decode_gemm_w8; quant.py: the contract); the
-prefill stays on the bf16 weights, which by then hold exactly the dequantised values."""
+After Engine.quantize_decoder() the step streams those matrices as e4m3fn bytes (vp_decode_gemm_w8) or as MXFP4 blocks (vp_decode_gemm_w4)
+instead (quant.py: the contracts); the prefill stays on the bf16 weights, which by then hold exactly the dequantised values."""
 from __future__ import annotations
 
 import os
@@ -93,9 +93,11 @@ class DecodeSession:
         # replayed vs 9.06 eager, 3.3 ms of host enqueue under it), so eager launches are the default; VP_DECODE_GRAPH=1 captures
         self.use_graph = os.environ.get("VP_DECODE_GRAPH", "0") == "1"
         self.replays = 0
-        # FP8 weight-only decoding (Engine.quantize_decoder): {fz key: (e4m3fn bytes, per-row scales)} of the matrices the step streams as fp8,
-        # or None (bf16).  Read once per session: a session never mixes the two, and stale copies were already dropped by fp8_weights().
-        self.fq = eng.fp8_weights()
+        # weight-only quantised decoding (Engine.quantize_decoder): {fz key: (e4m3fn bytes, per-row scales) | (e2m1 codes, block scale bytes)}
+        # of the matrices the step streams in fq_format, or None (bf16).  Read once per session: a session never mixes formats, and stale
+        # copies were already dropped by quantized_weights().
+        self.fq = eng.quantized_weights()
+        self.fq_format = eng.fq_format if self.fq is not None else None
 
     # ---------------------------------------------------------------------------------------------- prefill
     def prefill(self, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=16):
@@ -145,7 +147,9 @@ class DecodeSession:
         self.logits = e(B, V, dt=torch.float32)
         self.epi = ops.EPI_SWIGLU_IL if eng.gu_interleaved else ops.EPI_SWIGLU_HALVES
         shapes = [(nqkv, H, 0), (H, nh * hd, 0), (2 * I, H, self.epi), (H, I, 0), (V, H, 0)]
-        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep, w8) for N, K, ep in shapes for w8 in ((False, True) if self.fq else (False,)))
+        w4 = self.fq_format == "mxfp4"                           # the kernels the step can call: bf16 (lm_head may stay bf16) and the format's own
+        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep, w8=q and not w4, w4=q and w4) for N, K, ep in shapes
+                 for q in ((False, True) if self.fq else (False,)))
         self.gws = e(max(1, nb // 4), dt=torch.float32) if nb > 0 else None
         Smax = self.cache.Smax
         self.nsplit = ops.decode_attn_splits(B, nkv, Smax)
@@ -153,10 +157,12 @@ class DecodeSession:
         self.cos, self.sin = eng.rope(max(Smax, 1))
 
     def _gemm(self, a, key, **kw):
-        """One skinny GEMM of the step on weight `key`: its fp8 copy when the session decodes from fp8 weights, else the bf16 weight."""
+        """One skinny GEMM of the step on weight `key`: its quantised copy when the session decodes from one, else the bf16 weight."""
         q = self.fq.get(key) if self.fq else None
         if q is None:
             return ops.decode_gemm(a, self.eng.fz[key], **kw)
+        if self.fq_format == "mxfp4":
+            return ops.decode_gemm(a, q[0], w_block_scale=q[1], **kw)
         return ops.decode_gemm(a, q[0], w_scale=q[1], **kw)
 
     def _step_launches(self):

@@ -20,6 +20,7 @@ fp32 grads, Adam moments) so the DP all-reduce and the fused AdamW are one launc
 """
 from __future__ import annotations
 
+import gc
 import os
 
 import math
@@ -173,7 +174,8 @@ class Engine:
         self.lm_chunk_rows = lm_chunk_rows
         self.rank, self.world = 0, 1
         self.fz = {}           # frozen, kernel-ready weights
-        self.fq = None         # fp8 copies of the decoder matrices (quantize_decoder), or None
+        self.fq = None         # quantised copies of the decoder matrices (quantize_decoder), or None
+        self.fq_format = None  # "e4m3" | "mxfp4": the format of the copies in fq (None while there are none)
         self.ps = None         # ParamStore
         self._rope = {}
         self._plan_cache = {}          # per-batch splice plans (small LRU-ish cache: identical batches reuse their tables)
@@ -236,7 +238,7 @@ class Engine:
         cfg, dev = self.cfg, self.dev
         d = lambda t: t.detach().to(device=dev, dtype=BF16).contiguous()
         fz = self.fz = {}
-        self.fq = None                                           # fp8 copies (quantize_decoder) belong to the weights they were made from
+        self.fq = self.fq_format = None                          # quantised copies (quantize_decoder) belong to the weights they were made from
         # ---- CLIP tower (both transformers naming generations: with / without ".vision_model")
         vp = "model.vision_tower.vision_tower.vision_model."
         if vp + "embeddings.class_embedding" not in W:
@@ -347,6 +349,11 @@ class Engine:
         if train_llm:
             self._alias_llm_weights()
         self._build_static()
+        # an engine holds gigabytes of device memory, and a discarded one is often reachable only through a reference cycle (a hook that wraps
+        # one of its bound methods is enough): the cycle collector then frees it at some later allocation of its choosing.  Loading is when
+        # that memory is needed, so collect here: the device memory of discarded engines is back before the first step, and a step's peak
+        # allocation does not depend on the collector's timing
+        gc.collect()
 
     # ------------------------------------------------------------------------------------------ IFT: trainable LLM
     def _fused_range(self, names):
@@ -400,51 +407,60 @@ class Engine:
             for k in ("wqkv", "wgu", "wo", "wd"):
                 ops.transpose(fz[o + k], out=fz[o + k + "_T"])
 
-    # ------------------------------------------------------------------------------------------ FP8 weight-only decode
-    def quantize_decoder(self, lm_head=False):
-        """FP8 weight-only decoding for generate() (quant.py: the contract; stands in for the reference's load_8bit, builder.py:26-34).  Every
-        decoder matrix the decode step reads (per layer wqkv, wo, wgu, wd; lm_head when asked) is quantised to e4m3fn bytes with per-row
-        power-of-two scales, WITH write-back: the engine's bf16 weights become the dequantised model (exact), so prefill, the training forward
-        and logits_of see the weights the decode step streams as fp8.  The bf16 copy stays (prefill needs it).  The fp8 copies live in
-        `self.fq` beside `fz`; DecodeSession uses them while they are current (fp8_weights()).  Calling it again on unchanged weights gives the same model.
+    # ------------------------------------------------------------------------------------------ FP8 / MXFP4 weight-only decode
+    def quantize_decoder(self, lm_head=False, fmt="e4m3"):
+        """Weight-only quantised decoding for generate() (quant.py: the contracts; stands in for the reference's load_8bit / load_4bit,
+        builder.py:26-34).  Every decoder matrix the decode step reads (per layer wqkv, wo, wgu, wd; lm_head when asked) is quantised,
+        fmt="e4m3": to e4m3fn bytes with per-row power-of-two scales, fmt="mxfp4": to packed e2m1 codes with one e8m0 scale byte per block
+        of 32 k; either way WITH write-back: the engine's bf16 weights become the dequantised model (exact), so prefill, the training forward
+        and logits_of see the weights the decode step streams.  The bf16 copy stays (prefill needs it).  The copies live in `self.fq` beside
+        `fz` (`self.fq_format` names their format); DecodeSession uses them while they are current (quantized_weights()).  Calling it again
+        on unchanged weights gives the same model; calling it with the other format re-quantises the (already written-back) weights.
         On an engine whose decoder trains (train_llm) the write-back changes the bf16 shadow only; the fp32 master keeps the un-quantised
         weights.  state_dict() of a mirror then returns dequantised values for its bf16 Parameters (they alias the shadow), and the next
         optimizer step rebuilds the shadow from master + update: quantising for an evaluation does not damage the training run, it is
-        undone by the next step (and the fp8 copies are dropped then, fp8_weights()).  On a frozen decoder the write-back is permanent
+        undone by the next step (and the copies are dropped then, quantized_weights()).  On a frozen decoder the write-back is permanent
         until load_weights."""
+        if fmt not in ("e4m3", "mxfp4"):
+            raise ValueError(f"quantize_decoder: fmt {fmt!r} (e4m3 | mxfp4)")
+        quant = ops.quant_rows_e4m3 if fmt == "e4m3" else ops.quant_blocks_mxfp4
         fz = self.fz
         keys = [f"dec.{l}.{k}" for l in range(self.cfg.num_hidden_layers) for k in ("wqkv", "wo", "wgu", "wd")] + (["lm_head"] if lm_head else [])
         fq = {}
         for k in keys:
-            fq[k] = ops.quant_rows_e4m3(fz[k], writeback=True)
+            fq[k] = quant(fz[k], writeback=True)
         if getattr(self, "train_llm", False):
             self.ps.version += 1                                 # the shadow changed under the derived caches
         self.refresh_transposes()                                # the dgrad copies follow the written-back weights
-        self.fq = fq
+        self.fq, self.fq_format = fq, fmt
         self._fq_version = self.ps.version if self.ps is not None else None
         self._fq_warned = False
         return self
 
-    def fp8_weights(self):
-        """{fz key: (q uint8 [N, K], scale fp32 [N])} while the fp8 copies match the bf16 weights, else None.  On an engine whose decoder
-        trains, any change of the parameter store after quantize_decoder (optimizer step, load, in-place edit folded in by _sync_trainable)
-        makes them stale: they are dropped, with one warning, and decoding goes through the bf16 kernels."""
+    def quantized_weights(self):
+        """{fz key: (q uint8 [N, K], scale fp32 [N])} (e4m3) or {fz key: (q uint8 [N, K/2], e uint8 [N, K/32])} (mxfp4) while the quantised
+        copies match the bf16 weights, else None.  On an engine whose decoder trains, any change of the parameter store after quantize_decoder
+        (optimizer step, load, in-place edit folded in by _sync_trainable) makes them stale: they are dropped, with one warning, and decoding
+        goes through the bf16 kernels."""
         fq = self.fq
         if fq is None:
             return None
         if getattr(self, "train_llm", False) and self.ps.version != self._fq_version:
-            self.fq = None
+            self.fq = self.fq_format = None
             if not self._fq_warned:
                 self._fq_warned = True
                 import warnings
-                warnings.warn("decoder weights changed after quantize_decoder(): the fp8 copies are stale and were dropped; generate() decodes "
-                              "through the bf16 kernels (call quantize_for_generation() again to re-quantise)", RuntimeWarning, stacklevel=2)
+                warnings.warn("decoder weights changed after quantize_decoder(): the quantised copies are stale and were dropped; generate() "
+                              "decodes through the bf16 kernels (call quantize_for_generation() / quantize_for_generation_4bit() again to "
+                              "re-quantise)", RuntimeWarning, stacklevel=2)
             return None
         return fq
 
+    fp8_weights = quantized_weights                               # the name from before there was a second format
+
     def dequantized(self):
-        """True while generate() decodes from fp8 weights (and the bf16 weights are their dequantised values)."""
-        return self.fp8_weights() is not None
+        """True while generate() decodes from quantised weights (and the bf16 weights are their dequantised values)."""
+        return self.quantized_weights() is not None
 
     def _gfused(self, key):
         """fp32 gradient view of a fused weight (same layout as the fused bf16 view)."""

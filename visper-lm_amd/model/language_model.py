@@ -414,6 +414,16 @@ class EngineModule(nn.Module):
             self._get_engine().quantize_decoder(lm_head=lm_head)
         return self
 
+    def quantize_for_generation_4bit(self, lm_head=False):
+        """MXFP4 weight-only decoding for generate(): the load_4bit half of the same reference option, here OCP MXFP4 decoder weights (e2m1
+        codes, one power-of-two scale byte per block of 32; Engine.quantize_decoder(fmt="mxfp4"); quant.py documents the contract).
+        Everything quantize_for_generation() says holds: the bf16 weights become the dequantised model, generate() keeps its signature,
+        training afterwards drops the copies with one warning.  Calling it on a model quantised to 8 bits re-quantises.  Returns self."""
+        with torch.no_grad():
+            self._sync_trainable()                               # external edits first: the copies are made from current weights
+            self._get_engine().quantize_decoder(lm_head=lm_head, fmt="mxfp4")
+        return self
+
     def reload_frozen(self):
         """Call after load_state_dict(): rebuilds the engine's fused / pre-transposed frozen weights."""
         self._engine = None

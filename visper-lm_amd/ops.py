@@ -658,21 +658,30 @@ def adamw_(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
 EPI_SWIGLU_IL, EPI_SWIGLU_HALVES = 4, 5
 
 
-def decode_gemm_ws_bytes(M, N, K, epi=EPI_NONE, w8=False):
-    return int(_lib.raw("vp_decode_gemm_w8_workspace_bytes" if w8 else "vp_decode_gemm_workspace_bytes", M, N, K, epi))
+def decode_gemm_ws_bytes(M, N, K, epi=EPI_NONE, w8=False, w4=False):
+    assert not (w8 and w4)
+    name = "vp_decode_gemm_w4_workspace_bytes" if w4 else ("vp_decode_gemm_w8_workspace_bytes" if w8 else "vp_decode_gemm_workspace_bytes")
+    return int(_lib.raw(name, M, N, K, epi))
 
 
-def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f32=False, out=None, ws=None, w_scale=None):
+def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f32=False, out=None, ws=None, w_scale=None, w_block_scale=None):
     """out[M, N] = epi(norm(a)[M, K] @ w[N, K]^T) for M <= 16 (vp_decode_gemm): weight-streaming, optional RMSNorm prologue (gamma norm_w),
     + residual, SwiGLU on the fused gate|up weight (epi EPI_SWIGLU_IL / EPI_SWIGLU_HALVES: out [M, N/2]), fp32 output (logits).
     ws: caller-owned fp32 workspace of at least decode_gemm_ws_bytes() (allocated here when None).
-    w_scale (fp32 [N]): w is uint8 [N, K] of e4m3fn bytes with one power-of-two scale per row (quant_rows_e4m3) -> vp_decode_gemm_w8."""
+    w_scale (fp32 [N]): w is uint8 [N, K] of e4m3fn bytes with one power-of-two scale per row (quant_rows_e4m3) -> vp_decode_gemm_w8.
+    w_block_scale (uint8 [N, K/32]): w is uint8 [N, K/2] of packed e2m1 codes with one e8m0 scale byte per block of 32 k
+    (quant_blocks_mxfp4) -> vp_decode_gemm_w4."""
     M, K, lda = _rows2d(a)
     N, K2, ldw = _rows2d(w)
-    w8 = w_scale is not None
+    w8, w4 = w_scale is not None, w_block_scale is not None
+    assert not (w8 and w4), "w_scale (e4m3 rows) and w_block_scale (mxfp4 blocks) exclude each other"
     if w8:
         assert K == K2 and a.dtype == BF16 and w.dtype == torch.uint8, (a.shape, w.shape, w.dtype)
         assert w_scale.dtype == torch.float32 and w_scale.is_contiguous() and w_scale.numel() == N, (w_scale.shape, w_scale.dtype, N)
+    elif w4:
+        assert K == 2 * K2 and K % 32 == 0 and a.dtype == BF16 and w.dtype == torch.uint8, (a.shape, w.shape, w.dtype)
+        assert w_block_scale.dtype == torch.uint8 and w_block_scale.dim() == 2 and tuple(w_block_scale.shape) == (N, K // 32) and \
+            w_block_scale.stride(1) == 1, (w_block_scale.shape, w_block_scale.dtype, N, K)
     else:
         assert K == K2 and a.dtype == BF16 and w.dtype == BF16, (a.shape, w.shape)
     nout = N // 2 if epi in (EPI_SWIGLU_IL, EPI_SWIGLU_HALVES) else N
@@ -681,11 +690,15 @@ def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f3
     _, _, ldc = _rows2d(out)
     ldr = 0 if residual is None else _rows2d(residual)[2]
     if ws is None:
-        nb = decode_gemm_ws_bytes(M, N, K, epi, w8)
+        nb = decode_gemm_ws_bytes(M, N, K, epi, w8, w4)
         ws = torch.empty(max(1, nb // 4), device=a.device, dtype=torch.float32) if nb > 0 else None
     if w8:
         _lib.call("vp_decode_gemm_w8", M, N, K, _p(a), lda, _p(w), ldw, _p(w_scale), _p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps),
                   int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
+        return out
+    if w4:
+        _lib.call("vp_decode_gemm_w4", M, N, K, _p(a), lda, _p(w), ldw, _p(w_block_scale), w_block_scale.stride(0), _p(out), ldc, _p(residual),
+                  ldr, _p(norm_w), float(eps), int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
         return out
     _lib.call("vp_decode_gemm", M, N, K, _p(a), lda, _p(w), ldw, _p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps), int(epi),
               1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
@@ -701,6 +714,18 @@ def quant_rows_e4m3(w, writeback=False):
     scale = torch.empty(N, device=w.device, dtype=torch.float32)
     _lib.call("vp_quant_rows_e4m3", N, K, _p(w), ldw, _p(q), K, _p(scale), 1 if writeback else 0, _stream())
     return q, scale
+
+
+def quant_blocks_mxfp4(w, writeback=False):
+    """bf16 [N, K] -> (q uint8 [N, K/2] of packed OCP e2m1 codes, e uint8 [N, K/32] of e8m0 scale bytes): one power-of-two scale per block
+    of 32 k, round to nearest, ties to the even code (quant.py: the contract; vp_quant_blocks_mxfp4).  writeback: w is overwritten in place
+    with the dequantised value bf16(q * 2^(e - 127)), which is exact."""
+    N, K, ldw = _rows2d(w)
+    assert w.dim() == 2 and w.dtype == BF16 and K % 32 == 0, (w.shape, w.dtype)
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    e = torch.empty(N, K // 32, device=w.device, dtype=torch.uint8)
+    _lib.call("vp_quant_blocks_mxfp4", N, K, _p(w), ldw, _p(q), K // 2, _p(e), K // 32, 1 if writeback else 0, _stream())
+    return q, e
 
 
 def decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv, D):

@@ -1,4 +1,5 @@
-"""FP8 weight-only decoding: the format contract, and its plain-torch CPU reference (host-only: importable without a GPU, no kernels).
+"""FP8 and MXFP4 weight-only decoding: the format contracts, and their plain-torch CPU references (host-only: importable without a GPU, no
+kernels).  The FP8 contract comes first; the MXFP4 contract is documented above its functions, further down.
 
 The reference loads a checkpoint for evaluation with `load_pretrained_model(..., load_8bit=..., load_4bit=...)` (ola_vlm/model/builder.py:26-34),
 which goes through bitsandbytes.  That route does not exist on this part; what gfx950 has natively is OCP FP8, so `generate()` can stream its
@@ -56,3 +57,70 @@ def dequantize(q, scale):
     """fp32 [N, K] = e4m3fn(q) * scale[:, None] (exact; every value is representable in bf16)."""
     v = q.detach().cpu().view(torch.float8_e4m3fn).to(torch.float32).double()
     return (v * scale.detach().cpu().double()[:, None]).float()
+
+
+# ------------------------------------------------------------------------------------------------ MXFP4 (4-bit weight-only decoding)
+# The 4-bit half of the reference's load_8bit / load_4bit: OCP MXFP4, which gfx950 converts to bf16 natively with the block scale applied by
+# the conversion itself.  The contract (vp_quant_blocks_mxfp4 computes exactly this on the device through the integer arithmetic of
+# csrc/mxfp4.h, vp_decode_gemm_w4 consumes it):
+#
+#   * elements OCP e2m1: codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 is the sign.  Two codes per byte: element k of a row lives in byte
+#              k // 2, even k in the low nibble.  Stored as uint8 [N, K/2], row-major.
+#   * blocks   32 consecutive k of one row (K % 32 == 0); one e8m0 byte per block, uint8 [N, K/32], scale 2^(byte - 127).
+#   * scale    the smallest power of two with absmax / s <= 6: the block's largest magnitude lands in (3, 6], nothing saturates.  The exponent
+#              is clamped below at -120, so every nonzero dequantised value is a normal bf16 number (>= 2^-121) and neither the conversion
+#              nor the MFMA depends on a denormal mode; a clamped block's values may all round to zero.  A block of zeros gets byte 127.
+#   * range    weights are finite.  Below bf16's topmost binade (|w| < 2^127) the byte is at most 252 and q * s is exact; a block whose absmax
+#              lies in [2^127, 2^128) gets byte 252 or 253 and can round up to 6 * 2^126, which bf16 does not hold: outside the contract,
+#              as for e4m3.
+#   * rounding w / s is exact; round to nearest on the e2m1 grid, ties to the even code.  The sign bit is the weight's sign bit, also where the
+#              value rounds to zero.
+#   * exact    q * s is a 2-bit significand times a power of two: exactly representable in bf16, so write-back makes the bf16 weights the
+#              dequantised model, as for e4m3.
+#   * error    block-wise |w - q s| <= s * step / 2 with step 0.5 for |w / s| < 2, 1 for < 4, 2 above.
+#   * again    quantising the dequantised weights again gives the same VALUES: a scale halves when the block's largest code rounded down to
+#              3, and a block that rounded to all zeros gets byte 127.
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+MXFP4_MIN_SCALE_EXP = -120
+_E2M1_CODE_OF_HALVES = (0, 1, 2, 3, 4, -1, 5, -1, 6, -1, -1, -1, 7)     # code of a grid value given in units of 0.5
+
+
+def block_scale_exps_mxfp4(w):
+    """int64 [N, K/32]: exponent se of every block's power-of-two scale (the e8m0 byte is se + 127)."""
+    N, K = w.shape
+    assert K % MXFP4_BLOCK == 0, K
+    a = w.detach().abs().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK).amax(dim=2).double()
+    m, e = torch.frexp(a)                                       # a = m 2^e, m in [0.5, 1): exact in float64 for bf16 subnormals as well
+    se = e.to(torch.int64) - 3 + (m > 0.75).to(torch.int64)    # 6 = 0.75 * 2^3
+    se = se.clamp(min=MXFP4_MIN_SCALE_EXP)
+    return torch.where(a == 0, torch.zeros_like(se), se)
+
+
+def quantize_blocks_mxfp4(w_bf16):
+    """bf16 [N, K] -> (q uint8 [N, K/2] of packed e2m1 codes, e uint8 [N, K/32] of e8m0 scale bytes) on the CPU."""
+    assert w_bf16.dim() == 2 and w_bf16.dtype == torch.bfloat16, (w_bf16.shape, w_bf16.dtype)
+    w = w_bf16.detach().cpu()
+    N, K = w.shape
+    se = block_scale_exps_mxfp4(w)
+    s = torch.ldexp(torch.ones_like(se, dtype=torch.float64), se)
+    t = (w.double().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) / s[:, :, None]).view(N, K)      # exact: |t| <= 6
+    at = t.abs()
+    step = torch.where(at < 2, 0.5, torch.where(at < 4, 1.0, 2.0)).double()
+    r = torch.round(at / step) * step                           # half to even: the even multiple of the step is the even code
+    code = torch.tensor(_E2M1_CODE_OF_HALVES, dtype=torch.int64)[(r * 2).to(torch.int64)]
+    assert (code >= 0).all()
+    code = code | (torch.signbit(w).to(torch.int64) << 3)
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+    return q.contiguous(), (se + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(q, e):
+    """fp32 [N, K] = e2m1(q) * 2^(e - 127) per block (exact; every value is representable in bf16)."""
+    q, e = q.detach().cpu(), e.detach().cpu()
+    N, K = q.shape[0], q.shape[1] * 2
+    code = torch.stack([q & 0xf, q >> 4], dim=2).view(N, K).to(torch.int64)
+    v = torch.tensor(E2M1_VALUES, dtype=torch.float64)[code & 7]
+    v = torch.where((code & 8) != 0, -v, v)
+    s = torch.ldexp(torch.ones(e.shape, dtype=torch.float64), e.to(torch.int64) - 127)
+    return (v.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * s[:, :, None]).view(N, K).float()
