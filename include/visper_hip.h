@@ -274,6 +274,32 @@ long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit);
 int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts, const void* v,
                    long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                    vp_stream_t stream);
+/* FP8 KV cache: the cache of generate() in OCP e4m3fn bytes with one power-of-two fp32 scale per (token, KV head) — the row contract of
+ * vp_quant_rows_e4m3 with row length D (s = 2^ceil(log2(absmax / 448)), a zero head: s = 1, round to nearest even, nothing saturates, no NaN
+ * byte; quant.py: quantize_kv_heads).  K is quantised after RoPE, V as projected.  Every dequantised value is a bf16 number, so each writer
+ * can also (or instead) write the dequantised rows into a bf16 cache, which vp_decode_attn then reads: the same model on the bf16 kernel.
+ * vp_quant_kv_e4m3 (the prefill's cache writer): src bf16, n token rows of `heads` heads of D elements (2 Hkv for a k|v row), row stride
+ *   ld_src elements -> Q uint8 rows (stride ldq bytes) + scale fp32 [n, heads] rows (stride ld_scale elements), and / or deq bf16 rows
+ *   (stride ldd elements).  Q and scale go together; Q / scale or deq may be NULL, not both.  src is read only.  D a multiple of 8, at most
+ *   128; ld_src, ldq, ldd multiples of 8; src / deq 16-byte, Q 8-byte aligned.
+ * vp_decode_rope_append_kv8: vp_decode_rope_append (q_out is bit-identical to it) whose row pos[b] receives the quantised rotated k and the
+ *   quantised v: bytes ([B, Smax, Hkv, D] views, strides in bytes) + scales ([B, Smax, Hkv] views, strides in elements), and / or their
+ *   dequantised values in bf16 caches (strides in elements).  The four byte / scale pointers go together, the two bf16 pointers go together;
+ *   either set may be NULL, not both.  Rows with pos[b] outside [0, Smax) are not written.  D a multiple of 16, at most 128.
+ * vp_decode_attn_kv8: vp_decode_attn on the byte cache: k / v uint8 (strides in bytes, multiples of 16, bases 16-byte aligned), k_scale /
+ *   v_scale fp32 (strides in elements).  The bytes are converted exactly in registers; the key's scale multiplies its finished dot product,
+ *   the value row's scale multiplies its softmax weight (exact power-of-two products in fp32).  Same window / kv_len / nsplit conventions,
+ *   same workspace (vp_decode_attn_workspace_bytes), same fixed-order combine (bit-identical run to run), same shapes and error codes. */
+int vp_quant_kv_e4m3(long n, int heads, int D, const void* src, long ld_src, void* Q, long ldq, float* scale, long ld_scale, void* deq,
+                     long ldd, vp_stream_t stream);
+int vp_decode_rope_append_kv8(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_bytes, long k_bs,
+                              long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs, long ks_ts, float* v_scale,
+                              long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq, long vd_bs, long vd_ts,
+                              const float* cos_t, const float* sin_t, const int* pos, int Smax, vp_stream_t stream);
+int vp_decode_attn_kv8(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                       const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale, long vs_bs,
+                       long vs_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
+                       vp_stream_t stream);
 /* x[i] += delta for n int32 on the device (the per-sequence position / length counters of a decode step, advanced without a host round trip) */
 int vp_add_i32(long n, int* x, int delta, vp_stream_t stream);
 

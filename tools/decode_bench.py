@@ -19,6 +19,13 @@ process: the bf16 kernels on the written-back weights, the fp8 leg, the mxfp4 le
 below the fastest fp8 run.
 
   python tools/decode_bench.py --model llama3 --weights mxfp4 --out profiles/decode_bench_llama3_mxfp4.json
+
+--kv fp8: the engine is quantised to --weights (bf16: left as it is) and stays in that format; the bf16-cache leg and the fp8-cache leg
+(kv_cache_dtype="fp8_e4m3": e4m3fn bytes + one scale per (token, KV head)) alternate, --repeats runs each, in one process on the same
+engine and prompts.  The JSON carries every run and the cache bytes of both legs.  A cell is a "gain" only if the slowest fp8-cache run lies
+below the fastest bf16-cache run.
+
+  python tools/decode_bench.py --model phi3 --weights mxfp4 --kv fp8 --out profiles/decode_bench_phi3_kvfp8.json
 """
 import argparse
 import json
@@ -55,10 +62,10 @@ def prompt(eng, B, text_tokens, seed=0):
     return ids, images
 
 
-def time_decode(eng, B, new, text_tokens, use_graph):
+def time_decode(eng, B, new, text_tokens, use_graph, kv=None):
     from visper_lm_amd import decode
     ids, images = prompt(eng, B, text_tokens)
-    sess = decode.DecodeSession(eng)
+    sess = decode.DecodeSession(eng, kv_cache_dtype=kv)
     sess.use_graph = use_graph
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -82,7 +89,8 @@ def time_decode(eng, B, new, text_tokens, use_graph):
     per_tok = e0.elapsed_time(e1) / (new - 1)
     enq.sort()
     return dict(B=B, prompt_rows=int(sess.cache.lens_host.max()) - new, prefill_ms=round(prefill_ms, 2), ms_per_token=round(per_tok, 4),
-                host_enqueue_ms_per_token_median=round(enq[len(enq) // 2], 4), graph=use_graph, tokens_timed=new - 1)
+                host_enqueue_ms_per_token_median=round(enq[len(enq) // 2], 4), graph=use_graph, tokens_timed=new - 1,
+                kv_cache_bytes=int(sess.cache.nbytes))
 
 
 def fp8_legs(eng, B, new, text_tokens, repeats, use_graph):
@@ -134,6 +142,27 @@ def mxfp4_legs(eng, fq8, B, new, text_tokens, repeats, use_graph):
                 runs=legs["bf16"] + legs["fp8"] + legs["mxfp4"])
 
 
+def kv_legs(eng, weights, B, new, text_tokens, repeats, use_graph):
+    """bf16-cache and fp8-cache legs alternately on one engine -> dict with every run, the cache bytes of both legs, the medians, the verdict"""
+    names = {"bf16": "bf16", "fp8": "fp8_e4m3"}
+    legs = {k: [] for k in names}
+    for _ in range(repeats):
+        for leg, kv in names.items():
+            r = time_decode(eng, B, new, text_tokens, use_graph, kv=kv)
+            r.update(weights=weights, kv=leg)
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    t = {k: [r["ms_per_token"] for r in v] for k, v in legs.items()}
+    gain = max(t["fp8"]) < min(t["bf16"])
+    cb = {k: v[0]["kv_cache_bytes"] for k, v in legs.items()}
+    return dict(B=B, graph=use_graph, repeats=repeats, weights=weights, kv_bf16_ms_per_token=t["bf16"], kv_fp8_ms_per_token=t["fp8"],
+                kv_bf16_median=med(t["bf16"]), kv_fp8_median=med(t["fp8"]), kv_fp8_over_kv_bf16=round(med(t["fp8"]) / med(t["bf16"]), 4),
+                slowest_kv_fp8=max(t["fp8"]), fastest_kv_bf16=min(t["bf16"]), verdict="gain" if gain else "no gain",
+                kv_bf16_cache_bytes=cb["bf16"], kv_fp8_cache_bytes=cb["fp8"], kv_fp8_over_kv_bf16_bytes=round(cb["fp8"] / cb["bf16"], 4),
+                runs=legs["bf16"] + legs["fp8"])
+
+
 def weight_bytes(eng):
     cfg = eng.cfg
     H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
@@ -154,6 +183,8 @@ def main():
                     help="fp8: bf16 leg, then fp8 leg, on the same quantised engine; mxfp4: bf16, fp8 and mxfp4 legs on the engine quantised to mxfp4")
     ap.add_argument("--repeats", type=int, default=3, help="--weights fp8 / mxfp4: runs of each leg, alternating")
     ap.add_argument("--graph", action="store_true", help="--weights fp8 / mxfp4: time the captured step instead of eager launches")
+    ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: at the chosen --weights, bf16-cache and fp8-cache legs alternately on one engine, --repeats runs each")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
@@ -161,7 +192,24 @@ def main():
     dec_b, head_b = weight_bytes(eng)
     res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
                roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
-    if a.weights == "fp8":
+    if a.kv == "fp8":
+        if a.weights != "bf16":
+            eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")
+        cfg = eng.cfg
+        res.update(weights=a.weights, kv="fp8", lm_head_quantised=a.weights != "bf16", cells=[],
+                   kv_bytes_per_token_bf16=2 * 2 * cfg.num_key_value_heads * cfg.head_dim * cfg.num_hidden_layers,
+                   kv_bytes_per_token_fp8=2 * cfg.num_key_value_heads * (cfg.head_dim + 4) * cfg.num_hidden_layers)
+        for B in [int(x) for x in a.batches.split(",")]:
+            if a.profile:                                         # kernel-trace run: the fp8-cache leg alone, captured step
+                r = time_decode(eng, B, a.new, a.text, True, kv="fp8_e4m3")
+                r.update(weights=a.weights, kv="fp8")
+                res["runs"].append(r)
+                print(json.dumps(r), flush=True)
+                continue
+            cell = kv_legs(eng, a.weights, B, a.new, a.text, a.repeats, a.graph)
+            res["runs"] += cell.pop("runs")
+            res["cells"].append(cell)
+    if a.kv == "bf16" and a.weights == "fp8":
         eng.quantize_decoder(lm_head=True)
         res.update(weights="fp8", lm_head_fp8=True, fp8_roofline_ms_per_token_8tbps=round((dec_b + head_b) / 2 / 8e12 * 1e3, 3), cells=[])
         for B in [int(x) for x in a.batches.split(",")]:
@@ -176,7 +224,7 @@ def main():
             cell["bf16_weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 8e12 * 1e3 / cell["bf16_median"], 3)
             res["runs"] += cell.pop("runs")
             res["cells"].append(cell)
-    if a.weights == "mxfp4":
+    if a.kv == "bf16" and a.weights == "mxfp4":
         from visper_lm_amd import ops
         eng.quantize_decoder(lm_head=True, fmt="mxfp4")
         fq8 = {k: ops.quant_rows_e4m3(eng.fz[k]) for k in eng.fq}            # e4m3 copies of the written-back weights, no second write-back
@@ -193,7 +241,7 @@ def main():
             cell = mxfp4_legs(eng, fq8, B, a.new, a.text, a.repeats, a.graph)
             res["runs"] += cell.pop("runs")
             res["cells"].append(cell)
-    for B in ([] if a.weights != "bf16" else [int(x) for x in a.batches.split(",")]):
+    for B in ([] if a.weights != "bf16" or a.kv != "bf16" else [int(x) for x in a.batches.split(",")]):
         for g in ((True,) if a.profile else (True, False)):
             r = time_decode(eng, B, a.new, a.text, g)
             kv_bytes_per_pos = 2 * 2 * eng.cfg.num_key_value_heads * eng.cfg.head_dim * eng.cfg.num_hidden_layers

@@ -80,6 +80,10 @@ _SIGS = {
     "vp_decode_rope_append": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, p, p, i, p],
     "vp_decode_attn_workspace_bytes": [i, i, i, i, i],
     "vp_decode_attn": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, p, i, f, i, p, p],
+    # FP8 KV cache (e4m3fn bytes + one power-of-two scale per (token, KV head); quant.py: quantize_kv_heads)
+    "vp_quant_kv_e4m3": [l, i, i, p, l, p, l, p, l, p, l, p],
+    "vp_decode_rope_append_kv8": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, p, p, i, p],
+    "vp_decode_attn_kv8": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, p, i, f, i, p, p],
     "vp_add_i32": [l, p, i, p],
     "vp_ce_fwd_bwd": [l, i, p, l, p, p, f, i, p],
     "vp_emb_loss_workspace": [i, i, l],

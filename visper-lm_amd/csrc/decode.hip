@@ -840,6 +840,303 @@ __global__ void add_i32_kernel(int* __restrict__ x, long n, int delta) {
   if (i < n) x[i] += delta;
 }
 
+// ---------------------------------------------------------------- FP8 (e4m3) KV cache ---------------
+// The third member of the e4m3 / MXFP4 family: the cache itself in OCP e4m3fn bytes with one power-of-two fp32 scale per (token, KV head) —
+// the row contract of fp8_e4m3.h with row length D (quant.py: quantize_kv_heads).  K is quantised after RoPE, V as projected.
+//  - quant_kv_e4m3_kernel: the prefill sink.  One (token, head) row per lane group: absmax -> scale -> bytes (and / or the dequantised
+//    values as bf16 rows of a bf16 cache: the emulated mode, which the bf16 decode attention then reads).
+//  - decode_rope_append_kv8_kernel: decode_rope_append_kernel (the same rounding points: q is bit-identical) with one lane group per head, so
+//    that the D rotated elements of a k head (the D elements of a v head) meet for their absmax; row pos[b] receives bytes + scale.
+//  - decode_attn_split_kv8_kernel: decode_attn_split_kernel with byte operands: a 16-byte load carries 16 elements, a key row takes half the
+//    lanes and a block pass covers twice the keys.  The bytes are converted exactly in registers (v_cvt_scalef32_pk_bf16_fp8, scale 1); the k
+//    scale multiplies the finished dot product, the v scale multiplies p_j before the P V accumulation (both exact power-of-two products in
+//    fp32).  Partials in decode_attn_split_kernel's layout: decode_attn_combine_kernel and the workspace are shared.
+struct KvDst {                               // one of k / v: bytes + scales (q, s: both or neither) and / or dequantised bf16 rows (d)
+  uint8_t* q; long q_bs, q_ts;               // strides in bytes
+  float* s; long s_bs, s_ts;                 // [B, Smax, Hkv] fp32, strides in elements
+  bf16_t* d; long d_bs, d_ts;                // strides in elements
+};
+
+// 8 bf16 of one head -> 8 e4m3fn bytes of v / 2^se and their dequantised values
+__device__ __forceinline__ void kv8_quant8(const bf16x8 v, int se, u32x2& q, bf16x8& d) {
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t b = vp_e4m3_quant((uint16_t)v[j], se);
+    if (j < 4) lo |= b << (8 * j); else hi |= b << (8 * (j - 4));
+    d[j] = (short)vp_e4m3_dequant_bf16(b, se);
+  }
+  q[0] = lo;
+  q[1] = hi;
+}
+
+__device__ __forceinline__ uint32_t kv8_absmax8(const bf16x8 v, uint32_t am) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[j] & 0x7fffu);
+  return am;
+}
+
+// n token rows of `heads` heads (2 Hkv for a k|v row); lph lanes per head (a power of two >= D / 8 that divides 64: a head never straddles a
+// wave), lane sl owns elements sl * 8 .. sl * 8 + 7.  Every lane of the block runs every shuffle (the trip count is block-uniform).
+__global__ __launch_bounds__(256) void quant_kv_e4m3_kernel(const bf16_t* __restrict__ src, long ld_src, uint8_t* __restrict__ Q, long ldq,
+                                                            float* __restrict__ scale, long ld_scale, bf16_t* __restrict__ deq, long ldd,
+                                                            long n, int heads, int D, int lph) {
+  const long total = n * heads * lph;
+  for (long base = blockIdx.x * 256L; base < total; base += gridDim.x * 256L) {
+    const long i = base + threadIdx.x;
+    const long grp = i / lph;
+    const int sl = (int)(i % lph);
+    const bool act = i < total && sl * 8 < D;
+    const long t = grp / heads;
+    const long off = (grp % heads) * D + sl * 8;
+    bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act) v = *(const bf16x8*)(src + t * ld_src + off);
+    uint32_t am = kv8_absmax8(v, 0);
+    for (int o = lph >> 1; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+    if (act) {
+      const int se = vp_e4m3_scale_exp(am);
+      u32x2 qv;
+      bf16x8 d;
+      kv8_quant8(v, se, qv, d);
+      if (Q) {
+        *(u32x2*)(Q + t * ldq + off) = qv;
+        if (sl == 0) scale[t * ld_scale + grp % heads] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
+      }
+      if (deq) *(bf16x8*)(deq + t * ldd + off) = d;
+    }
+  }
+}
+
+// qkv [B, ldq] rows (q heads | k heads | v heads); lph lanes per head (a power of two >= D / 16), lane sl owns the 8-wide vector sl of the
+// head's first half and its partner in the second half (the rotation pair for q / k)
+__global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo,
+                                                                     long ldq, KvDst kd, KvDst vd, const float* __restrict__ cs,
+                                                                     const float* __restrict__ sn, const int* __restrict__ pos, int B, int Hq,
+                                                                     int Hkv, int D, int Smax, int lph) {
+  const int half = D >> 1, vph = half >> 3;
+  const int per_b = (Hq + 2 * Hkv) * lph;
+  const long total = (long)B * per_b;
+  for (long base = blockIdx.x * 256L; base < total; base += gridDim.x * 256L) {
+    const long i = base + threadIdx.x;
+    const bool in = i < total;
+    const int b = in ? (int)(i / per_b) : 0, r = in ? (int)(i % per_b) : 0;
+    const int h = r / lph, sl = r % lph;
+    const bool act = in && sl < vph;
+    const bool rot = h < Hq + Hkv;
+    const int p = pos[b];
+    bf16x8 oa = {0, 0, 0, 0, 0, 0, 0, 0}, ob = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act) {
+      const bf16_t* src = qkv + (long)b * ldqkv + (long)h * D + sl * 8;
+      const bf16x8 a = *(const bf16x8*)src, bb = *(const bf16x8*)(src + half);
+      if (rot) {
+        const int pc = min(max(p, 0), Smax - 1);
+        const float* c = cs + (long)pc * half + sl * 8;
+        const float* s = sn + (long)pc * half + sl * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float x1 = bf2f((bf16_t)a[j]), x2 = bf2f((bf16_t)bb[j]);
+          oa[j] = (short)f2bf(bfround(x1 * c[j]) + bfround(-x2 * s[j]));
+          ob[j] = (short)f2bf(bfround(x2 * c[j]) + bfround(x1 * s[j]));
+        }
+      } else {
+        oa = a;
+        ob = bb;
+      }
+    }
+    uint32_t am = kv8_absmax8(ob, kv8_absmax8(oa, 0));
+    for (int o = lph >> 1; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+    if (act && h < Hq) {
+      bf16_t* dst = qo + (long)b * ldq + (long)h * D + sl * 8;
+      *(bf16x8*)dst = oa;
+      *(bf16x8*)(dst + half) = ob;
+    } else if (act && p >= 0 && p < Smax) {                         // never write outside the cache
+      const int hk = rot ? h - Hq : h - Hq - Hkv;
+      const int se = vp_e4m3_scale_exp(am);
+      u32x2 qa, qb;
+      bf16x8 da, db;
+      kv8_quant8(oa, se, qa, da);
+      kv8_quant8(ob, se, qb, db);
+      uint8_t* qp = rot ? kd.q : vd.q;
+      if (qp) {
+        qp += (rot ? (long)b * kd.q_bs + (long)p * kd.q_ts : (long)b * vd.q_bs + (long)p * vd.q_ts) + (long)hk * D + sl * 8;
+        *(u32x2*)qp = qa;
+        *(u32x2*)(qp + half) = qb;
+        if (sl == 0) {
+          float* sp = rot ? kd.s + (long)b * kd.s_bs + (long)p * kd.s_ts : vd.s + (long)b * vd.s_bs + (long)p * vd.s_ts;
+          sp[hk] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
+        }
+      }
+      bf16_t* dp = rot ? kd.d : vd.d;
+      if (dp) {
+        dp += (rot ? (long)b * kd.d_bs + (long)p * kd.d_ts : (long)b * vd.d_bs + (long)p * vd.d_ts) + (long)hk * D + sl * 8;
+        *(bf16x8*)dp = da;
+        *(bf16x8*)(dp + half) = db;
+      }
+    }
+  }
+}
+
+// 16 e4m3fn bytes -> 16 fp32, exact: gfx950 converts a pair of fp8 to a bf16 pair in one instruction (as dg8_cvt), a bf16 is the upper half
+// of its fp32
+__device__ __forceinline__ void da8_cvt(const u32x4 q, float* f) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t x = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[i], 1.0f, false));
+    const uint32_t y = __builtin_bit_cast(uint32_t, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[i], 1.0f, true));
+    f[4 * i] = __builtin_bit_cast(float, x << 16);
+    f[4 * i + 1] = __builtin_bit_cast(float, x & 0xffff0000u);
+    f[4 * i + 2] = __builtin_bit_cast(float, y << 16);
+    f[4 * i + 3] = __builtin_bit_cast(float, y & 0xffff0000u);
+  }
+}
+
+// grid (nsplit, Hkv, B), 256 threads; the partials of decode_attn_split_kernel.  k / v: e4m3fn bytes (strides in bytes), ksc / vsc: the
+// fp32 scale of (b, token, hkv) (strides in elements)
+template <int D, int G>
+__global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t* __restrict__ q, long q_bs, const uint8_t* __restrict__ k,
+                                                                    long k_bs, long k_ts, const float* __restrict__ ksc, long ks_bs, long ks_ts,
+                                                                    const uint8_t* __restrict__ v, long v_bs, long v_ts,
+                                                                    const float* __restrict__ vsc, long vs_bs, long vs_ts,
+                                                                    const int* __restrict__ kv_len, int Smax, int window, float scale,
+                                                                    float* __restrict__ ws, int Hkv) {
+  constexpr int LPK = D <= 32 ? 2 : (D <= 64 ? 4 : 8);          // lanes per key row (16-byte vectors of 16 elements; D = 96 leaves 2 of 8 idle)
+  constexpr int KPB = 256 / LPK;                                 // key rows per block pass
+  __shared__ float sc[G][DA_CHMAX];
+  __shared__ float red[4][G][D];
+  __shared__ float ml[G][2];
+  const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int sl = tid % LPK, ko = tid / LPK, e = sl * 16;
+  const bool act = e < D;
+  const int len = min(kv_len[b], Smax);
+  const int lo = window > 0 ? max(0, len - window) : 0;
+  const int nk = max(0, len - lo);
+  const int ch = (nk + ns - 1) / ns;
+  const int s0 = lo + min(nk, s * ch), s1 = lo + min(nk, (s + 1) * ch);
+  const int cnt = s1 - s0;                                       // <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
+  float* out = ws + (((long)b * Hkv + hkv) * ns + s) * G * (D + 2);
+  const uint8_t* kb = k + (long)b * k_bs + (long)hkv * D + e;
+  const uint8_t* vb = v + (long)b * v_bs + (long)hkv * D + e;
+  const float* ksb = ksc + (long)b * ks_bs + hkv;
+  const float* vsb = vsc + (long)b * vs_bs + hkv;
+  {
+    float qf[G][16];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        bf16x8 qv = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (act) qv = *(const bf16x8*)(q + (long)b * q_bs + (long)(hkv * G + g) * D + e + u * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[g][u * 8 + j] = bf2f((bf16_t)qv[j]) * (scale * DA_LOG2E);
+      }
+    // scores (log2 domain) -> LDS
+    for (int j0 = 0; j0 < cnt; j0 += 2 * KPB) {                   // two key rows per lane and pass: both loads are issued before either converts
+      u32x4 kq[2];
+      float ksj[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = j0 + u * KPB + ko;
+        kq[u] = u32x4{0, 0, 0, 0};
+        ksj[u] = 0.f;
+        if (act && j < cnt) kq[u] = *(const u32x4*)(kb + (long)(s0 + j) * k_ts);
+        if (sl == 0 && j < cnt) ksj[u] = ksb[(long)(s0 + j) * ks_ts];
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = j0 + u * KPB + ko;
+        float kf[16];
+        da8_cvt(kq[u], kf);
+        float d[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          float a = 0.f;
+#pragma unroll
+          for (int x = 0; x < 16; ++x) a += qf[g][x] * kf[x];
+#pragma unroll
+          for (int o = LPK / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+          d[g] = a * ksj[u];                                       // the key's scale on the finished dot product
+        }
+        if (sl == 0 && j < cnt)
+#pragma unroll
+          for (int g = 0; g < G; ++g) sc[g][j] = d[g];
+      }
+    }
+  }
+  __syncthreads();
+  // per head: max, exp2, sum (wave w handles heads w, w + 4, ...)
+  for (int g = w; g < G; g += 4) {
+    float mx = -INFINITY;
+    for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, sc[g][j]);
+    mx = wave_max(mx);
+    float l = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+      const float pj = exp2f(sc[g][j] - mx);
+      sc[g][j] = pj;
+      l += pj;
+    }
+    l = wave_sum(l);
+    if (lane == 0) { ml[g][0] = mx; ml[g][1] = l; }
+  }
+  __syncthreads();
+  // P V
+  float acc[G][16];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int x = 0; x < 16; ++x) acc[g][x] = 0.f;
+  for (int j0 = 0; j0 < cnt; j0 += 2 * KPB) {
+    u32x4 vq[2];
+    float vsj[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = j0 + u * KPB + ko;
+      vq[u] = u32x4{0, 0, 0, 0};
+      vsj[u] = 0.f;
+      if (act && j < cnt) {
+        vq[u] = *(const u32x4*)(vb + (long)(s0 + j) * v_ts);
+        vsj[u] = vsb[(long)(s0 + j) * vs_ts];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = j0 + u * KPB + ko;
+      if (act && j < cnt) {
+        float vf[16];
+        da8_cvt(vq[u], vf);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float pj = sc[g][j] * vsj[u];                      // the value row's scale on p_j
+#pragma unroll
+          for (int x = 0; x < 16; ++x) acc[g][x] += pj * vf[x];
+        }
+      }
+    }
+  }
+  // key groups of a wave (lanes sl, sl + LPK, ...) -> one, then the 4 waves in order
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int x = 0; x < 16; ++x)
+#pragma unroll
+      for (int o = LPK; o < 64; o <<= 1) acc[g][x] += __shfl_xor(acc[g][x], o, 64);
+  if (lane < LPK && act)
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int x = 0; x < 16; ++x) red[w][g][e + x] = acc[g][x];
+  __syncthreads();
+  for (int i = tid; i < G * D; i += 256) {
+    const int g = i / D, dd = i % D;
+    out[g * (D + 2) + dd] = ((red[0][g][dd] + red[1][g][dd]) + red[2][g][dd]) + red[3][g][dd];
+  }
+  if (tid < G) {
+    out[tid * (D + 2) + D] = cnt > 0 ? ml[tid][0] : -INFINITY;
+    out[tid * (D + 2) + D + 1] = cnt > 0 ? ml[tid][1] : 0.f;
+  }
+}
+
 extern "C" {
 
 int vp_add_i32(long n, int* x, int delta, hipStream_t stream) {
@@ -1043,6 +1340,94 @@ int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long 
 #undef DA_LAUNCH
   hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, G, D, nsplit);
   return vp_check_launch("vp_decode_attn");
+}
+
+int vp_quant_kv_e4m3(long n, int heads, int D, const void* src, long ld_src, void* Q, long ldq, float* scale, long ld_scale, void* deq,
+                     long ldd, hipStream_t stream) {
+  VP_REQUIRE(src && (Q || deq), VP_ERR_BAD_ARG, "vp_quant_kv_e4m3: null src, or neither a byte (Q) nor a bf16 (deq) destination");
+  VP_REQUIRE(!Q == !scale, VP_ERR_BAD_ARG, "vp_quant_kv_e4m3: Q and scale go together (both or neither)");
+  VP_REQUIRE(n > 0 && n <= (1L << 24) && heads > 0 && heads <= 1024, VP_ERR_BAD_ARG, "vp_quant_kv_e4m3: n = %ld, heads = %d", n, heads);
+  VP_REQUIRE(D >= 8 && D <= 128 && D % 8 == 0, VP_ERR_UNSUPPORTED_SHAPE, "vp_quant_kv_e4m3: head_dim %d (a multiple of 8, at most 128)", D);
+  const long row = (long)heads * D;
+  VP_REQUIRE(ld_src >= row && ld_src % 8 == 0 && (((uintptr_t)src) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_quant_kv_e4m3: ld_src = %ld (>= heads * D = %ld, a multiple of 8), src 16-byte aligned", ld_src, row);
+  VP_REQUIRE(!Q || (ldq >= row && ldq % 8 == 0 && (((uintptr_t)Q) & 7) == 0 && ld_scale >= heads && (((uintptr_t)scale) & 3) == 0),
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_quant_kv_e4m3: ldq = %ld (>= %ld, a multiple of 8), ld_scale = %ld (>= %d), Q 8-byte aligned", ldq,
+             row, ld_scale, heads);
+  VP_REQUIRE(!deq || (ldd >= row && ldd % 8 == 0 && (((uintptr_t)deq) & 15) == 0), VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_quant_kv_e4m3: ldd = %ld (>= %ld, a multiple of 8), deq 16-byte aligned", ldd, row);
+  const int lph = D <= 16 ? 2 : (D <= 32 ? 4 : (D <= 64 ? 8 : 16));
+  const long total = n * heads * lph;
+  hipLaunchKernelGGL(quant_kv_e4m3_kernel, dim3((unsigned)min(4096L, (total + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)src, ld_src,
+                     (uint8_t*)Q, ldq, scale, ld_scale, (bf16_t*)deq, ldd, n, heads, D, lph);
+  return vp_check_launch("vp_quant_kv_e4m3");
+}
+
+int vp_decode_rope_append_kv8(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_bytes, long k_bs,
+                              long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs, long ks_ts, float* v_scale,
+                              long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq, long vd_bs, long vd_ts,
+                              const float* cos_t, const float* sin_t, const int* pos, int Smax, hipStream_t stream) {
+  VP_REQUIRE(qkv && q_out && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: null pointer");
+  const bool bytes = k_bytes != nullptr, deq = k_deq != nullptr;
+  VP_REQUIRE(bytes == (v_bytes != nullptr) && bytes == (k_scale != nullptr) && bytes == (v_scale != nullptr) && deq == (v_deq != nullptr),
+             VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: k / v bytes and scales go together, k / v bf16 destinations go together");
+  VP_REQUIRE(bytes || deq, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: neither a byte nor a bf16 destination");
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: bad sizes");
+  VP_REQUIRE(D % 16 == 0 && D >= 16 && D <= 128 && ldqkv % 8 == 0 && ldq % 8 == 0 && ((((uintptr_t)qkv) | ((uintptr_t)q_out)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: head_dim %d must be a multiple of 16 (at most 128), strides multiples of 8", D);
+  VP_REQUIRE(!bytes || (k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
+                        ((((uintptr_t)k_bytes) | ((uintptr_t)v_bytes)) & 7) == 0),
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: byte strides must be multiples of 8, byte bases 8-byte aligned");
+  VP_REQUIRE(!deq || (kd_bs % 8 == 0 && kd_ts % 8 == 0 && vd_bs % 8 == 0 && vd_ts % 8 == 0 &&
+                      ((((uintptr_t)k_deq) | ((uintptr_t)v_deq)) & 15) == 0),
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: bf16 strides must be multiples of 8, bf16 bases 16-byte aligned");
+  const int lph = D <= 32 ? 2 : (D <= 64 ? 4 : 8);
+  const long total = (long)B * (Hq + 2 * Hkv) * lph;
+  const KvDst kd{(uint8_t*)k_bytes, k_bs, k_ts, k_scale, ks_bs, ks_ts, (bf16_t*)k_deq, kd_bs, kd_ts};
+  const KvDst vd{(uint8_t*)v_bytes, v_bs, v_ts, v_scale, vs_bs, vs_ts, (bf16_t*)v_deq, vd_bs, vd_ts};
+  hipLaunchKernelGGL(decode_rope_append_kv8_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
+                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, kd, vd, cos_t, sin_t, pos, B, Hq, Hkv, D, Smax, lph);
+  return vp_check_launch("vp_decode_rope_append_kv8");
+}
+
+int vp_decode_attn_kv8(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                       const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale, long vs_bs,
+                       long vs_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
+                       hipStream_t stream) {
+  VP_REQUIRE(q && k && v && k_scale && v_scale && o && kv_len, VP_ERR_BAD_ARG, "vp_decode_attn_kv8: null pointer");
+  VP_REQUIRE(workspace, VP_ERR_BAD_ARG, "vp_decode_attn_kv8: workspace is NULL (vp_decode_attn_workspace_bytes)");
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Smax > 0 && window >= 0, VP_ERR_BAD_ARG,
+             "vp_decode_attn_kv8: bad sizes (B %d, Hq %d, Hkv %d, Smax %d)", B, Hq, Hkv, Smax);
+  const int G = Hq / Hkv;
+  VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: head_dim %d (32 | 64 | 96 | 128)", D);
+  VP_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: Hq / Hkv = %d (1 | 2 | 4 | 8)", G);
+  VP_REQUIRE(nsplit >= 1 && nsplit <= 1024 && (long)nsplit * DA_CHMAX >= Smax, VP_ERR_UNSUPPORTED_SHAPE,
+             "vp_decode_attn_kv8: nsplit %d must cover Smax %d with at most %d keys per split", nsplit, Smax, DA_CHMAX);
+  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 16 == 0 && k_ts % 16 == 0 && v_bs % 16 == 0 && v_ts % 16 == 0 &&
+             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: q stride must be a multiple of 8 elements, k / v strides of 16 bytes, bases 16-byte aligned");
+  const dim3 grid(nsplit, Hkv, B);
+#define DA8_LAUNCH(DD, GG)                                                                                                             \
+  hipLaunchKernelGGL((decode_attn_split_kv8_kernel<DD, GG>), grid, dim3(256), 0, stream, (const bf16_t*)q, q_bs, (const uint8_t*)k,   \
+                     k_bs, k_ts, k_scale, ks_bs, ks_ts, (const uint8_t*)v, v_bs, v_ts, v_scale, vs_bs, vs_ts, kv_len, Smax, window,   \
+                     scale, workspace, Hkv)
+#define DA8_G(DD)                          \
+  switch (G) {                             \
+    case 1: DA8_LAUNCH(DD, 1); break;      \
+    case 2: DA8_LAUNCH(DD, 2); break;      \
+    case 4: DA8_LAUNCH(DD, 4); break;      \
+    default: DA8_LAUNCH(DD, 8); break;     \
+  }
+  switch (D) {
+    case 32: DA8_G(32); break;
+    case 64: DA8_G(64); break;
+    case 96: DA8_G(96); break;
+    default: DA8_G(128); break;
+  }
+#undef DA8_G
+#undef DA8_LAUNCH
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, G, D, nsplit);
+  return vp_check_launch("vp_decode_attn_kv8");
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 IFT classes — the multimodal splice, then HF's generation loop over `inputs_embeds`).
 
   prefill   the label-less training forward (build_plan(labels=None) -> _embed -> _decoder_fwd(compute_grads=False)) with every layer's
-            post-RoPE k / v rows copied into the cache; lm_head on each sequence's last valid row only
+            post-RoPE k / v rows copied (or, for an FP8 cache, quantised: vp_quant_kv_e4m3) into the cache; lm_head on each sequence's
+            last valid row only
   step      per layer: QKV (RMSNorm prologue) -> RoPE + KV append at pos[b] -> decode attention -> wo + residual -> gate_up (RMSNorm
             prologue, SwiGLU epilogue) -> down + residual; final norm folded into the fp32 lm_head launch; pos / kv_len += 1 on the device
 
@@ -10,7 +11,9 @@ Every per-token scalar (token ids, positions, cache lengths) lives on the device
 (single stream, no fork) and replayed for every token (VP_DECODE_GRAPH=1; the default is eager launches: capture did not pay, see below).  Decode reads the same kernel-ready weights
 _decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current.
 After Engine.quantize_decoder() the step streams those matrices as e4m3fn bytes (vp_decode_gemm_w8) or as MXFP4 blocks (vp_decode_gemm_w4)
-instead (quant.py: the contracts); the prefill stays on the bf16 weights, which by then hold exactly the dequantised values."""
+instead (quant.py: the contracts); the prefill stays on the bf16 weights, which by then hold exactly the dequantised values.
+Independently of the weights, the cache itself can be kept as e4m3fn bytes with one scale per (token, KV head) (kv_cache_dtype="fp8_e4m3":
+vp_decode_rope_append_kv8 / vp_decode_attn_kv8), or, for verification, as a bf16 cache of the dequantised values read by the bf16 kernels."""
 from __future__ import annotations
 
 import os
@@ -24,17 +27,41 @@ BF16 = torch.bfloat16
 I32 = torch.int32
 
 
-class KVCache:
-    """Per layer one [B, Smax, 2 * Hkv * D] bf16 buffer: each token row is k (Hkv * D) | v (Hkv * D), the layout of the k|v columns of the fused
-    qkv rows (the prefill copies a sequence's rows in one strided copy).  `lens`: int32 [2B] on the device = (pos [B] = tokens cached,
-    kv_len [B] = pos + 1: the keys the next step attends to, its own included); `lens_host` mirrors pos."""
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3", "fp8_e4m3_emulated")
 
-    def __init__(self, cfg, B, Smax, device):
+
+def resolve_kv_cache_dtype(name):
+    """None / "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" -> the canonical name (host-only; anything else is a ValueError)."""
+    if name is None:
+        return "bf16"
+    if isinstance(name, str) and name in KV_CACHE_DTYPES:
+        return name
+    raise ValueError(f"kv_cache_dtype {name!r}: choose one of {', '.join(KV_CACHE_DTYPES)} (None = bf16)")
+
+
+class KVCache:
+    """Per layer one [B, Smax, 2 * Hkv * D] buffer: each token row is k (Hkv * D) | v (Hkv * D), the layout of the k|v columns of the fused
+    qkv rows (the prefill writes a sequence's rows in one strided launch).  `lens`: int32 [2B] on the device = (pos [B] = tokens cached,
+    kv_len [B] = pos + 1: the keys the next step attends to, its own included); `lens_host` mirrors pos.
+    dtype "bf16": bf16 rows.  "fp8_e4m3": uint8 rows of e4m3fn bytes plus `scales`, per layer fp32 [B, Smax, 2 * Hkv] (k scales | v scales),
+    one power-of-two scale per (token, KV head) (quant.py: quantize_kv_heads): (D + 4) / 2D of the bf16 cache's bytes.
+    "fp8_e4m3_emulated": bf16 rows that hold the dequantised quantised values (the same model on the bf16 attention kernel)."""
+
+    def __init__(self, cfg, B, Smax, device, dtype="bf16"):
         nkv, hd = cfg.num_key_value_heads, cfg.head_dim
         self.B, self.Smax, self._hd = B, Smax, hd
-        self.kv = [torch.empty(B, Smax, 2 * nkv * hd, device=device, dtype=BF16) for _ in range(cfg.num_hidden_layers)]
+        self.dtype = resolve_kv_cache_dtype(dtype)
+        L = cfg.num_hidden_layers
+        fp8 = self.dtype == "fp8_e4m3"
+        self.kv = [torch.empty(B, Smax, 2 * nkv * hd, device=device, dtype=torch.uint8 if fp8 else BF16) for _ in range(L)]
+        self.scales = [torch.empty(B, Smax, 2 * nkv, device=device, dtype=torch.float32) for _ in range(L)] if fp8 else None
         self.lens = torch.zeros(2 * B, device=device, dtype=I32)
         self.lens_host = np.zeros(B, np.int64)
+
+    @property
+    def nbytes(self):
+        """bytes of the k / v storage (scales included)"""
+        return sum(t.numel() * t.element_size() for t in self.kv + (self.scales or []))
 
     def k(self, l):
         B, Smax, C = self.kv[l].shape
@@ -43,6 +70,13 @@ class KVCache:
     def v(self, l):
         B, Smax, C = self.kv[l].shape
         return self.kv[l].view(B, Smax, 2, -1)[:, :, 1].unflatten(-1, (-1, self._hd))
+
+    def k_scale(self, l):
+        """fp32 [B, Smax, Hkv] view ("fp8_e4m3" only)"""
+        return self.scales[l][:, :, :self.scales[l].shape[2] // 2]
+
+    def v_scale(self, l):
+        return self.scales[l][:, :, self.scales[l].shape[2] // 2:]
 
     @property
     def pos(self):
@@ -85,9 +119,12 @@ def text_plan(eng, input_ids, attention_mask):
 class DecodeSession:
     """One generate() call: the cache, the preallocated step buffers and (optionally) the captured step."""
 
-    def __init__(self, eng):
+    def __init__(self, eng, kv_cache_dtype=None):
         self.eng = eng
         self.cfg = eng.cfg
+        # the cache format (KVCache): the argument, else the engine's default (model.quantize_kv_cache_for_generation); independent of
+        # the weight format below.  Resolved here, on the host, before any GPU work
+        self.kv_cache_dtype = resolve_kv_cache_dtype(kv_cache_dtype if kv_cache_dtype is not None else getattr(eng, "kv_cache_dtype", None))
         self.graph = None
         # capture measured on MI355X (profiles/decode_bench_*.json): no gain — the step is GPU-bound (Llama-3-8B B = 1: 9.01 ms/token
         # replayed vs 9.06 eager, 3.3 ms of host enqueue under it), so eager launches are the default; VP_DECODE_GRAPH=1 captures
@@ -112,14 +149,21 @@ class DecodeSession:
         B, S = plan["B"], plan["S"]
         lens = np.asarray(plan["lens_host"]).astype(np.int64)
         Smax = int(lens.max()) + int(max_new_tokens)
-        c = self.cache = KVCache(cfg, B, Smax, eng.dev)
+        c = self.cache = KVCache(cfg, B, Smax, eng.dev, self.kv_cache_dtype)
         cw = 2 * nkv * hd
+        kvd = self.kv_cache_dtype
 
         def sink(l, qkv):
             src = qkv.view(B, S, -1)
             for b in range(B):                                  # rows 0 .. len_b - 1 (the kernels' layout is left-aligned for either padding side)
                 n = int(lens[b])
-                ops.copy2d_(c.kv[l][b, :n], src[b, :n, nh * hd:nh * hd + cw])
+                rows = src[b, :n, nh * hd:nh * hd + cw]
+                if kvd == "bf16":
+                    ops.copy2d_(c.kv[l][b, :n], rows)
+                elif kvd == "fp8_e4m3":                          # bytes + one scale per (token, head)
+                    ops.quant_kv_e4m3(rows, hd, q_out=c.kv[l][b, :n], scale_out=c.scales[l][b, :n])
+                else:                                           # emulated: the dequantised values into the bf16 cache
+                    ops.quant_kv_e4m3(rows, hd, deq_out=c.kv[l][b, :n])
 
         dec = eng._decoder_fwd(x, plan, compute_grads=False, kv_sink=sink)
         H = cfg.hidden_size
@@ -176,8 +220,17 @@ class DecodeSession:
         for l in range(cfg.num_hidden_layers):
             o = f"dec.{l}."
             self._gemm(x, o + "wqkv", norm_w=fz[o + "ln1"], eps=eps, out=self.qkv, ws=self.gws)
-            ops.decode_rope_append(self.qkv, self.q, c.k(l), c.v(l), self.cos, self.sin, c.pos, nh, nkv, hd)
-            ops.decode_attn(self.q, c.k(l), c.v(l), c.kv_len, nh, window=window, nsplit=self.nsplit, out=self.att, ws=self.aws)
+            if self.kv_cache_dtype == "fp8_e4m3":
+                ops.decode_rope_append_kv8(self.qkv, self.q, self.cos, self.sin, c.pos, nh, nkv, hd, k_bytes=c.k(l), v_bytes=c.v(l),
+                                           k_scale=c.k_scale(l), v_scale=c.v_scale(l))
+                ops.decode_attn_kv8(self.q, c.k(l), c.v(l), c.k_scale(l), c.v_scale(l), c.kv_len, nh, window=window, nsplit=self.nsplit,
+                                    out=self.att, ws=self.aws)
+            else:
+                if self.kv_cache_dtype == "bf16":
+                    ops.decode_rope_append(self.qkv, self.q, c.k(l), c.v(l), self.cos, self.sin, c.pos, nh, nkv, hd)
+                else:                                           # emulated: the new row's dequantised values, read by the bf16 kernel
+                    ops.decode_rope_append_kv8(self.qkv, self.q, self.cos, self.sin, c.pos, nh, nkv, hd, k_deq=c.k(l), v_deq=c.v(l))
+                ops.decode_attn(self.q, c.k(l), c.v(l), c.kv_len, nh, window=window, nsplit=self.nsplit, out=self.att, ws=self.aws)
             self._gemm(self.att, o + "wo", residual=x, out=self.h1, ws=self.gws)
             self._gemm(self.h1, o + "wgu", norm_w=fz[o + "ln2"], eps=eps, epi=self.epi, out=self.act, ws=self.gws)
             xn = self.x[(l + 1) % 2]
@@ -232,14 +285,16 @@ def next_tokens(logits, do_sample=False, temperature=1.0, top_p=1.0, generator=N
 
 
 def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=20, do_sample=False, temperature=1.0,
-             top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False):
+             top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False,
+             kv_cache_dtype=None):
     """Greedy / sampled decoding of B prompts, each continuing at its own length -> LongTensor [B, n_new] of the new tokens only (rows that
-    finished are padded with pad_token_id after their EOS).  return_logits: also the fp32 logits [B, V] each token was chosen from."""
+    finished are padded with pad_token_id after their EOS).  return_logits: also the fp32 logits [B, V] each token was chosen from.
+    kv_cache_dtype: None (the engine's default, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" (KVCache)."""
     B = input_ids.shape[0]
     eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
     if pad_token_id is None:
         pad_token_id = eos[0] if eos else 0
-    sess = DecodeSession(eng)
+    sess = DecodeSession(eng, kv_cache_dtype)
     if use_graph is not None:
         sess.use_graph = bool(use_graph)
     if streamer is not None:

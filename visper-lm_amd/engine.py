@@ -176,6 +176,7 @@ class Engine:
         self.fz = {}           # frozen, kernel-ready weights
         self.fq = None         # quantised copies of the decoder matrices (quantize_decoder), or None
         self.fq_format = None  # "e4m3" | "mxfp4": the format of the copies in fq (None while there are none)
+        self.kv_cache_dtype = "bf16"   # generate()'s default KV cache format (decode.KV_CACHE_DTYPES); independent of the weight format
         self.ps = None         # ParamStore
         self._rope = {}
         self._plan_cache = {}          # per-batch splice plans (small LRU-ish cache: identical batches reuse their tables)

@@ -141,6 +141,10 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
         inputs = kwargs.get("input_ids")
     if inputs is None:
         raise ValueError("generate needs `inputs` (prompt token ids, base_ola_vlm.py:581)")
+    # the KV cache format (not an HF argument): None = the engine's default; an unknown name is refused here, before any GPU work
+    kv_cache_dtype = kwargs.pop("kv_cache_dtype", None)
+    if kv_cache_dtype is not None:
+        kv_cache_dtype = decode.resolve_kv_cache_dtype(kv_cache_dtype)
     with torch.no_grad():
         module._sync_trainable()
         eng = module._get_engine()
@@ -154,7 +158,7 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
             pad_token_id = getattr(module.config, "pad_token_id", None)
         return decode.generate(eng, inputs, attention_mask, images, gsz, max_new_tokens=max_new_tokens, do_sample=do_sample,
                                temperature=temperature, top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                               streamer=streamer, generator=generator)
+                               streamer=streamer, generator=generator, kv_cache_dtype=kv_cache_dtype)
 
 
 class _VisperStep(torch.autograd.Function):
@@ -424,6 +428,14 @@ class EngineModule(nn.Module):
             self._get_engine().quantize_decoder(lm_head=lm_head, fmt="mxfp4")
         return self
 
+    def quantize_kv_cache_for_generation(self, enable=True):
+        """FP8 KV cache for generate(): the cache is kept as OCP e4m3fn bytes with one power-of-two scale per (token, KV head) instead of
+        bf16 (quant.py documents the contract; decode.KVCache), about half the bytes a decode step reads and the cache occupies.  Sets the
+        default of generate()'s `kv_cache_dtype` argument ("fp8_e4m3"; enable=False: back to "bf16"); the argument still overrides it per
+        call.  Independent of quantize_for_generation() / _4bit(): every weight format runs with every cache format.  Returns self."""
+        self._get_engine().kv_cache_dtype = "fp8_e4m3" if enable else "bf16"
+        return self
+
     def reload_frozen(self):
         """Call after load_state_dict(): rebuilds the engine's fused / pre-transposed frozen weights."""
         self._engine = None
@@ -579,11 +591,13 @@ class _OlaCausalLMBase(OlaLlavaMetaForCausalLM, BaseOLA_VLM, EngineModule):
     _forward = forward
 
     def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
-                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None, **kwargs):
+                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None,
+                 kv_cache_dtype=None, **kwargs):
         """base_ola_vlm.py:579-616: with `images` the prompt is spliced (image features + task tokens, ola_arch.py:256-444); with
-        images=None it is the token embeddings alone (base_ola_vlm.py:606-607).  -> LongTensor [B, n_new] (new tokens only)."""
+        images=None it is the token embeddings alone (base_ola_vlm.py:606-607).  -> LongTensor [B, n_new] (new tokens only).
+        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated"."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
-                         pad_token_id, num_beams, use_cache, streamer, generator, **kwargs)
+                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype, **kwargs)
 
 
 class OlaLlavaLlamaForCausalLM(_OlaCausalLMBase):

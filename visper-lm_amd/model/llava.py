@@ -151,11 +151,13 @@ class _LlavaCausalLMBase(LlavaMetaForCausalLM, EngineModule):
         return CausalLMOutputWithPast(loss=loss, logits=logits, hidden_states=hidden_states)
 
     def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
-                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None, **kwargs):
+                 top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None,
+                 kv_cache_dtype=None, **kwargs):
         """llava_llama.py:122-153: images -> prepare_inputs_labels_for_multimodal's splice, else the token embeddings alone; then HF
-        generation over inputs_embeds.  -> LongTensor [B, n_new] (new tokens only)."""
+        generation over inputs_embeds.  -> LongTensor [B, n_new] (new tokens only).
+        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated"."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
-                         pad_token_id, num_beams, use_cache, streamer, generator, **kwargs)
+                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype, **kwargs)
 
 
 class LlavaLlamaForCausalLM(_LlavaCausalLMBase):

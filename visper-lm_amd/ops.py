@@ -765,6 +765,82 @@ def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=No
     return out
 
 
+def quant_kv_e4m3(src, D, q_out=None, scale_out=None, deq_out=None):
+    """The FP8 KV cache's prefill writer (vp_quant_kv_e4m3; quant.py: quantize_kv_heads): src bf16 [n, heads * D] token rows (a strided view,
+    e.g. the k|v columns of the fused qkv rows; read only) -> q_out uint8 [n, heads * D] e4m3fn bytes + scale_out fp32 [n, heads] (one
+    power-of-two scale per (token, head)), and / or deq_out bf16 [n, heads * D]: the dequantised values (exact).  The outputs are views of
+    the caches (row-strided); q_out and scale_out go together."""
+    n, C, ld_src = _rows2d(src)
+    assert src.dim() == 2 and src.dtype == BF16 and C % D == 0, (src.shape, src.dtype, D)
+    heads = C // D
+    assert (q_out is None) == (scale_out is None) and (q_out is not None or deq_out is not None), "bytes + scales and / or a bf16 destination"
+    ldq = lds = ldd = 0
+    if q_out is not None:
+        assert q_out.dtype == torch.uint8 and tuple(q_out.shape) == (n, C) and q_out.stride(1) == 1, (q_out.shape, q_out.dtype)
+        assert scale_out.dtype == torch.float32 and tuple(scale_out.shape) == (n, heads) and scale_out.stride(1) == 1, scale_out.shape
+        ldq, lds = q_out.stride(0), scale_out.stride(0)
+    if deq_out is not None:
+        assert deq_out.dtype == BF16 and tuple(deq_out.shape) == (n, C) and deq_out.stride(1) == 1, (deq_out.shape, deq_out.dtype)
+        ldd = deq_out.stride(0)
+    _lib.call("vp_quant_kv_e4m3", n, heads, D, _p(src), ld_src, _p(q_out), ldq, _p(scale_out), lds, _p(deq_out), ldd, _stream())
+    return q_out, scale_out, deq_out
+
+
+def _bsh(t):
+    """(batch stride, token stride) of a [B, Smax, Hkv] scale view whose last dim is contiguous"""
+    assert t.dim() == 3 and (t.stride(2) == 1 or t.shape[2] == 1), "scale view: [B, Smax, Hkv], heads contiguous"
+    return t.stride(0), t.stride(1)
+
+
+def decode_rope_append_kv8(qkv, q_out, cos_t, sin_t, pos, Hq, Hkv, D, k_bytes=None, v_bytes=None, k_scale=None, v_scale=None, k_deq=None,
+                           v_deq=None):
+    """decode_rope_append for the FP8 KV cache (vp_decode_rope_append_kv8): q -> q_out as there (bit-identical); row pos[b] of the byte
+    caches (uint8 [B, Smax, Hkv, D] views) and of the scales (fp32 [B, Smax, Hkv] views) receives the quantised rotated k and the quantised
+    v, and / or row pos[b] of the bf16 caches k_deq / v_deq their dequantised values."""
+    B, _, ldqkv = _rows2d(qkv)
+    bytes_, deq = k_bytes is not None, k_deq is not None
+    assert bytes_ or deq, "a byte cache and / or a bf16 cache"
+    a = [None, 0, 0] * 6
+    Smax = (k_bytes if bytes_ else k_deq).shape[1]
+    if bytes_:
+        for t in (k_bytes, v_bytes):
+            assert t.dtype == torch.uint8 and tuple(t.shape) == (B, Smax, Hkv, D), (t.shape, t.dtype)
+        for t in (k_scale, v_scale):
+            assert t.dtype == torch.float32 and tuple(t.shape) == (B, Smax, Hkv), (t.shape, t.dtype)
+        a[0:12] = [_p(k_bytes), *_bshd(k_bytes), _p(v_bytes), *_bshd(v_bytes), _p(k_scale), *_bsh(k_scale), _p(v_scale), *_bsh(v_scale)]
+    if deq:
+        for t in (k_deq, v_deq):
+            assert t.dtype == BF16 and tuple(t.shape) == (B, Smax, Hkv, D), (t.shape, t.dtype)
+        a[12:18] = [_p(k_deq), *_bshd(k_deq), _p(v_deq), *_bshd(v_deq)]
+    assert cos_t.shape[0] >= Smax and pos.dtype == torch.int32 and pos.numel() == B
+    _lib.call("vp_decode_rope_append_kv8", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out), q_out.stride(0), *a, _p(cos_t), _p(sin_t), _p(pos), Smax,
+              _stream())
+    return q_out
+
+
+def decode_attn_kv8(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+    """decode_attn on the FP8 KV cache (vp_decode_attn_kv8): q [B, Hq*D] rows, byte caches uint8 [B, Smax, Hkv, D], scales fp32
+    [B, Smax, Hkv], kv_len int32 [B] (device) -> o [B, Hq*D] bf16.  Same splits and workspace as decode_attn."""
+    B, Smax, Hkv, D = k_bytes.shape
+    assert k_bytes.dtype == torch.uint8 and v_bytes.dtype == torch.uint8 and tuple(v_bytes.shape) == (B, Smax, Hkv, D)
+    assert k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32 and tuple(k_scale.shape) == tuple(v_scale.shape) == (B, Smax, Hkv)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if nsplit is None:
+        nsplit = decode_attn_splits(B, Hkv, Smax)
+    if out is None:
+        out = torch.empty(B, Hq * D, device=q.device, dtype=BF16)
+    if ws is None:
+        ws = torch.empty(_lib.raw("vp_decode_attn_workspace_bytes", B, Hq, Hkv, D, nsplit) // 4, device=q.device, dtype=torch.float32)
+    kb, kt = _bshd(k_bytes)
+    vb, vt = _bshd(v_bytes)
+    ksb, kst = _bsh(k_scale)
+    vsb, vst = _bsh(v_scale)
+    _lib.call("vp_decode_attn_kv8", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_bytes), kb, kt, _p(k_scale), ksb, kst, _p(v_bytes), vb, vt,
+              _p(v_scale), vsb, vst, _p(out), out.stride(0), _p(kv_len), int(window), float(scale), int(nsplit), _p(ws), _stream())
+    return out
+
+
 def add_i32_(x, delta=1):
     assert x.dtype == torch.int32 and x.is_contiguous()
     _lib.call("vp_add_i32", x.numel(), _p(x), int(delta), _stream())

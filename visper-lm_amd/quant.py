@@ -1,5 +1,5 @@
-"""FP8 and MXFP4 weight-only decoding: the format contracts, and their plain-torch CPU references (host-only: importable without a GPU, no
-kernels).  The FP8 contract comes first; the MXFP4 contract is documented above its functions, further down.
+"""FP8 and MXFP4 weight-only decoding and the FP8 KV cache: the format contracts, and their plain-torch CPU references (host-only: importable
+without a GPU, no kernels).  The FP8 contract comes first; the MXFP4 contract and the KV cache's are documented above their functions, further down.
 
 The reference loads a checkpoint for evaluation with `load_pretrained_model(..., load_8bit=..., load_4bit=...)` (ola_vlm/model/builder.py:26-34),
 which goes through bitsandbytes.  That route does not exist on this part; what gfx950 has natively is OCP FP8, so `generate()` can stream its
@@ -124,3 +124,36 @@ def dequantize_mxfp4(q, e):
     v = torch.where((code & 8) != 0, -v, v)
     s = torch.ldexp(torch.ones(e.shape, dtype=torch.float64), e.to(torch.int64) - 127)
     return (v.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * s[:, :, None]).view(N, K).float()
+
+
+# ------------------------------------------------------------------------------------------------ FP8 KV cache (e4m3 per (token, KV head))
+# The third member of the family: after the weights, the KV cache is what a decode step reads (at B = 8 far more than the 4-bit weights), and
+# it caps batch and context length.  `generate(..., kv_cache_dtype="fp8_e4m3")` keeps it in 8 bits.  The contract (vp_quant_kv_e4m3 and
+# vp_decode_rope_append_kv8 compute exactly this on the device through the integer arithmetic of csrc/fp8_e4m3.h, vp_decode_attn_kv8
+# consumes it):
+#
+#   * unit     the D elements of one (token, KV head) of K form one row; the same holds for V.
+#   * format   the e4m3 ROW contract above with row length D: OCP `e4m3fn` bytes, one fp32 power-of-two scale per (token, head),
+#              s = 2^ceil(log2(absmax / 448)); a zero head gets s = 1; round to nearest even; nothing saturates; no NaN byte.
+#   * K        is quantised AFTER RoPE: the rotated bf16 row the bf16 cache would have stored is what gets quantised.  V as projected.
+#   * storage  per layer bytes uint8 [B, Smax, 2*Hkv*D] (token row = k heads | v heads, the bf16 cache's layout) and scales fp32
+#              [B, Smax, 2*Hkv] (k scales | v scales): (D + 4) / 2D of the bf16 cache, 0.516 at D = 128 and 0.521 at D = 96.
+#   * exact    q * s is a bf16 number, so a bf16 cache holding the dequantised rows ("fp8_e4m3_emulated") read by the bf16 attention kernel
+#              is the SAME mathematical model as the byte cache read by vp_decode_attn_kv8: the decode path's own bounds compare the two.
+#   * product  the attention keeps q in bf16, converts the bytes in registers (exact), multiplies a key's finished fp32 dot product by its
+#              scale and a value row's softmax weight by its scale (exact power-of-two products in fp32).
+#   * error    per element as for the rows contract: |x - q s| <= 2^-4 |x| in the scaled normal range, 2^-10 s below it.
+def quantize_kv_heads(x_bf16, Hkv, D):
+    """bf16 [n, Hkv*D] (the k heads, or the v heads, of n tokens) -> (q uint8 [n, Hkv*D], scale fp32 [n, Hkv]) on the CPU: quantize_rows_pow2
+    on the [n*Hkv, D] view."""
+    assert x_bf16.dim() == 2 and x_bf16.shape[1] == Hkv * D, (x_bf16.shape, Hkv, D)
+    n = x_bf16.shape[0]
+    q, s = quantize_rows_pow2(x_bf16.detach().cpu().reshape(n * Hkv, D))
+    return q.view(n, Hkv * D), s.view(n, Hkv)
+
+
+def dequantize_kv_heads(q, s, Hkv, D):
+    """fp32 [n, Hkv*D] = e4m3fn(q) * s per (token, head) (exact; every value is representable in bf16): dequantize on the [n*Hkv, D] view."""
+    n = q.shape[0]
+    assert q.shape[1] == Hkv * D and tuple(s.shape) == (n, Hkv), (q.shape, s.shape, Hkv, D)
+    return dequantize(q.detach().cpu().reshape(n * Hkv, D), s.detach().cpu().reshape(n * Hkv)).view(n, Hkv * D)
