@@ -177,7 +177,12 @@ int vp_minmax_norm(int B, long n, const void* x, void* y, vp_stream_t stream);
  * fp32 softmax, PV), HF CLIPAttention (non-causal), PerceiverAttention (resampler.py:46-75; scale d^-1/4
  * on q and k == d^-1/2 on the product).  Tensors are [B,S,H,D] views (strides in elements, multiples of 8; 16-byte
  * aligned bases).  lse: fp32 [B,Hq,Sq] (log2 domain).  vp_attn_bwd's `delta` is a caller-owned fp32 workspace of
- * 3*B*Hq*Sq floats (row dots dO.O, then interleaved (lse, delta) pairs for the DMA-fed dK/dV kernel). */
+ * 3*B*Hq*Sq floats (row dots dO.O, then interleaved (lse, delta) pairs for the DMA-fed dK/dV kernel).
+ * Mask: key j is visible to query row i iff j < kv_len[b] (kv_len NULL: Skv), causal: j <= i + Skv - Sq, window > 0: j > i + Skv - Sq - window.
+ * A query row with NO visible key (a window together with kv_len: rows past kv_len + window - 1 - (Skv - Sq) of a right-padded sample) is
+ * defined: the forward writes o = 0 and lse = -1e30 for it; the backward, given that lse, writes dq = 0 for it and adds nothing of it to
+ * dk / dv (keys >= kv_len get exact zeros).  HF's eager softmax yields NaN for such a row; its loss terms are masked out there.
+ * Undefined for these entry points: kv_len[b] = 0, and causal with Sq > Skv. */
 int vp_attn_fwd(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void* q, long q_bs, long q_ts, const void* k,
                 long k_bs, long k_ts, const void* v, long v_bs, long v_ts, void* o, long o_bs, long o_ts, float* lse,
                 const int* kv_len, int causal, int window, float scale, vp_stream_t stream);

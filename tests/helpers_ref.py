@@ -1,6 +1,6 @@
 """Plain torch references of the bandwidth-bound helper kernels (csrc/elementwise.hip, csrc/conv.hip, the transposes of csrc/gemm.hip) and of
-masked attention with its gradients, shared by tests/test_helpers_host.py (CPU), tests/test_helpers_gpu.py and
-tests/test_attention_generic_gpu.py.
+masked attention with its gradients and lse, shared by tests/test_helpers_host.py (CPU), tests/test_helpers_gpu.py,
+tests/test_attention_generic_gpu.py and tests/test_attention_d128_gpu.py (whose cases, inputs and comparisons are the last section here).
 
 Every reference runs in the float dtype `dt` it is given (fp32: what a kernel with fp32 math computes; fp64: the truth), restates the
 kernel's documented bf16 rounding points with `bfr`, and leaves the LAST rounding of a bf16 output out (the caller applies `.to(BF)` where
@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import regimes as R
-from regimes import BF, bfr, gen
+from regimes import BF, bfr, gen, randn
 
 # The grid caps of the launchers (csrc/elementwise.hip, csrc/conv.hip): blocks of 256 threads; a kernel with more work items than
 # cap * 256 runs its grid-stride loop a second time.
@@ -211,43 +211,87 @@ def sumsq(x, dt=torch.float32, mut=None):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def attention(q, k, v, do, causal, kv_len=None, window=0, dt=torch.float32, mut=None):
-    """q / do [B, Sq, Hq, D], k / v [B, Skv, Hkv, D]: HF-eager masked softmax attention (the mask of test_kernels_gpu.attn_ref: causal with
-    offset Skv - Sq, keys > i - window, keys < kv_len[b]) and its gradients written out: P = softmax(S), dV = P^T dO, dS = P (dO V^T - rowsum(dO O)),
-    dQ = dS K / sqrt(D), dK = dS^T Q / sqrt(D).  Mutants: `kvlen_ignored_dkdv` (the dK / dV pass recomputes P from the row statistics without the
-    kv_len term of its mask), `window_off_by_one` (keys >= i - window)."""
-    B, Sq, Hq, D = q.shape
-    Skv, Hkv = k.shape[1], k.shape[2]
-    rep = Hq // Hkv
-    qq, dd = q.to(dt).transpose(1, 2), do.to(dt).transpose(1, 2)
-    kk = k.to(dt).transpose(1, 2).repeat_interleave(rep, dim=1)
-    vv = v.to(dt).transpose(1, 2).repeat_interleave(rep, dim=1)
-    sc = 1.0 / math.sqrt(D)
-    s = qq @ kk.transpose(-1, -2) * sc
-    i = torch.arange(Sq)[:, None] + (Skv - Sq)
+LOG2E = 1.4426950408889634
+EMPTY_LSE = -1e30        # lse of a query row that sees no key (include/visper_hip.h)
+ATTENTION_MUTANTS = ["block_first_key_dropped", "offset_dropped_after_first_block", "window_off_by_one", "kvlen_ignored_dkdv", "empty_row_nan",
+                     "empty_row_uniform", "lse_natural_log", "lse_without_last_tile", "kv_head_modulo", "gqa_last_head_dropped_in_dkdv"]
+
+
+def attention_mask(B, Sq, Skv, causal, kv_len=None, window=0, mut=None):
+    """allow [B, 1, Sq, Skv]: the mask of test_kernels_gpu.attn_ref (causal with offset Skv - Sq, keys > i - window, keys < kv_len[b]).  Mutants:
+    `window_off_by_one` (keys >= i - window), `block_first_key_dropped` (key 256 is invisible to rows >= 256: a second 256-row block that starts
+    its key loop one key late), `offset_dropped_after_first_block` (Skv - Sq taken as 0 for rows >= 256)."""
+    off = torch.full((Sq, 1), Skv - Sq)
+    if mut == "offset_dropped_after_first_block":
+        off[256:] = 0
+    i = torch.arange(Sq)[:, None] + off
     j = torch.arange(Skv)[None, :]
     allow = torch.ones(Sq, Skv, dtype=torch.bool)
     if causal:
         allow &= j <= i
     if window > 0:
         allow &= (j >= i - window) if mut == "window_off_by_one" else (j > i - window)
+    if mut == "block_first_key_dropped" and Skv > 256:
+        allow[256:, 256] = False
     allow = allow[None, None].expand(B, 1, Sq, Skv).clone()
-    no_len = allow.clone()
     if kv_len is not None:
         for b in range(B):
             allow[b, :, :, kv_len[b]:] = False
+    return allow
+
+
+def attention(q, k, v, do, causal, kv_len=None, window=0, dt=torch.float32, mut=None):
+    """q / do [B, Sq, Hq, D], k / v [B, Skv, Hkv, D]: HF-eager masked softmax attention (attention_mask) and its gradients written out:
+    P = softmax(S), dV = P^T dO, dS = P (dO V^T - rowsum(dO O)), dQ = dS K / sqrt(D), dK = dS^T Q / sqrt(D); lse [B, Hq, Sq] = log2 sum_j exp(S_ij)
+    (the log2 domain of include/visper_hip.h).  A query row that sees no key (a window together with kv_len) has P = 0: o = 0, lse = EMPTY_LSE,
+    dq = 0, nothing added to dk / dv (HF-eager's softmax yields NaN there; the header defines the kernels' value).
+    Mutants (value-only): those of attention_mask; `kvlen_ignored_dkdv` (the dK / dV pass recomputes P from the row statistics without the kv_len
+    term of its mask); `empty_row_nan` (an empty row's P is softmax of an all-masked row: NaN); `empty_row_uniform` (its P is 1 / Skv: o = the mean
+    of all V); `lse_natural_log` (only lse changes); `lse_without_last_tile` (lse from the keys below the last started 64-key tile, everything else
+    honest); `kv_head_modulo` (q head h reads kv head h % Hkv, not h // rep); `gqa_last_head_dropped_in_dkdv` (the last q head of each group is
+    missing from dk / dv)."""
+    B, Sq, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    rep = Hq // Hkv
+    if mut == "kv_head_modulo":
+        spread = lambda t: t.repeat(1, rep, 1, 1)                                                      # head h <- kv head h % Hkv
+        gather = lambda t: t.reshape(B, rep, Hkv, Skv, D).sum(1)
+    else:
+        spread = lambda t: t.repeat_interleave(rep, dim=1)                                             # head h <- kv head h // rep
+        gather = lambda t: t.reshape(B, Hkv, rep, Skv, D)[:, :, :rep - (mut == "gqa_last_head_dropped_in_dkdv")].sum(2)
+    qq, dd = q.to(dt).transpose(1, 2), do.to(dt).transpose(1, 2)
+    kk, vv = spread(k.to(dt).transpose(1, 2)), spread(v.to(dt).transpose(1, 2))
+    sc = 1.0 / math.sqrt(D)
+    s = qq @ kk.transpose(-1, -2) * sc
+    allow = attention_mask(B, Sq, Skv, causal, kv_len, window, mut)
+    empty = ~allow.any(-1, keepdim=True)                                                               # [B, 1, Sq, 1]
     sm = s.masked_fill(~allow, float("-inf"))
-    lse = torch.logsumexp(sm, -1, keepdim=True)
-    P = torch.exp(sm - lse)
+    lse = torch.logsumexp(sm.masked_fill(empty, 0.0), -1, keepdim=True)                                # (a finite placeholder on empty rows)
+    P = torch.exp(sm - lse)                                                                            # exp(-inf) = 0 on empty rows
+    lse2 = (lse * LOG2E).masked_fill(empty, EMPTY_LSE)
+    if mut == "empty_row_nan":
+        P, lse2 = P.masked_fill(empty, float("nan")), lse2.masked_fill(empty, float("nan"))
+    elif mut == "empty_row_uniform":
+        P, lse2 = P.masked_fill(empty, 1.0 / Skv), lse2.masked_fill(empty, math.log2(Skv))
+    elif mut == "lse_natural_log":
+        lse2 = lse.masked_fill(empty, EMPTY_LSE)
+    elif mut == "lse_without_last_tile":
+        j = torch.arange(Skv)
+        last = (allow * j).amax(-1, keepdim=True)                                                      # the row's last visible key
+        below = allow & (j < last // 64 * 64)
+        none = ~below.any(-1, keepdim=True)
+        lse2 = (torch.logsumexp(s.masked_fill(~below, float("-inf")).masked_fill(none, 0.0), -1, keepdim=True) * LOG2E).masked_fill(none, EMPTY_LSE)
     o = P @ vv
-    Pk = torch.exp(s.masked_fill(~no_len, float("-inf")) - lse) if mut == "kvlen_ignored_dkdv" else P
+    Pk = P
+    if mut == "kvlen_ignored_dkdv":
+        Pk = torch.exp(s.masked_fill(~attention_mask(B, Sq, Skv, causal, None, window), float("-inf")) - lse)
     delta = (dd * o).sum(-1, keepdim=True)
     dP = dd @ vv.transpose(-1, -2)
     dS, dSk = P * (dP - delta), Pk * (dP - delta)
     dq = dS @ kk * sc
-    dk = (dSk.transpose(-1, -2) @ qq * sc).reshape(B, Hkv, rep, Skv, D).sum(2)
-    dv = (Pk.transpose(-1, -2) @ dd).reshape(B, Hkv, rep, Skv, D).sum(2)
-    return dict(o=o.transpose(1, 2), dq=dq.transpose(1, 2), dk=dk.transpose(1, 2), dv=dv.transpose(1, 2))
+    dk = gather(dSk.transpose(-1, -2) @ qq * sc)
+    dv = gather(Pk.transpose(-1, -2) @ dd)
+    return dict(o=o.transpose(1, 2), dq=dq.transpose(1, 2), dk=dk.transpose(1, 2), dv=dv.transpose(1, 2), lse=lse2[..., 0].expand(B, Hq, Sq))
 
 
 # ------------------------------------------------------------------------------------------------ comparisons
@@ -330,3 +374,123 @@ def flips(got, want):
     a, b = got.detach().cpu().contiguous().view(torch.int16).int(), want.detach().cpu().contiguous().view(torch.int16).int()
     d = (a - b).abs()
     return float((d > 0).float().mean()), int(d.max())
+
+
+# ------------------------------------------------------------------------------------------------ D = 128 / 96 attention at block edges
+# tests/ATTENTION_D128.md maps each case to the path it enters.  (B, Hq, Hkv, Sq, Skv, causal, window, kv_len); each runs at D = 128 and D = 96.
+D128_CASES = {
+    "three-blocks-one-row": (1, 2, 1, 513, 513, True, 0, None),
+    "offset-across-blocks": (1, 4, 2, 300, 600, True, 0, None),
+    "window-kstart": (2, 2, 2, 600, 600, True, 70, None),
+    "window-kvlen-empty": (2, 2, 1, 600, 600, True, 64, [600, 130]),
+    "noncausal-kvlen": (1, 2, 2, 260, 700, False, 0, [650]),
+    "gqa-permuted": (1, 8, 2, 520, 520, True, 0, None),
+}
+D128_DIMS = (128, 96)
+D128_BLOCK = 256         # query rows / keys per block of the forward and of the default backward
+# the case each mutant is aimed at
+D128_MUTANT_CASE = {
+    "block_first_key_dropped": "three-blocks-one-row", "offset_dropped_after_first_block": "offset-across-blocks", "window_off_by_one": "window-kstart",
+    "kvlen_ignored_dkdv": "noncausal-kvlen", "empty_row_nan": "window-kvlen-empty", "empty_row_uniform": "window-kvlen-empty",
+    "lse_natural_log": "three-blocks-one-row", "lse_without_last_tile": "noncausal-kvlen", "kv_head_modulo": "gqa-permuted",
+    "gqa_last_head_dropped_in_dkdv": "gqa-permuted"}
+# bf16 roundings on the path to each output (the fp64 reference restates none): o: P as a bf16 MFMA operand, the output; dv: P, the output;
+# dq, dk: the two of o (through delta = rowsum(dO o O) from the bf16 o), dS as a bf16 MFMA operand, the output.  The same points in all five
+# kernels (attention_bwd64.h:29; attention_d128.h: pk / dsk packs of the DMA-ring pair, pf of the forward; attention.hip pack8 of the 16-row forward).
+D128_ROUNDINGS = dict(o=2, dv=2, dq=4, dk=4)
+
+
+def d128_inputs(name, D, kind):
+    """kind "random": N(0, 1) bf16 q, k, v, do.  kind "exact": q = 0, k random, v[j, d] = (d == j % D): every visible score is exactly 0, so
+    m = 0, p = 1, l = n (the number of visible keys) and the accumulators hold integer counts."""
+    B, Hq, Hkv, Sq, Skv, causal, window, kvl = D128_CASES[name]
+    seed = 500 + 10 * sorted(D128_CASES).index(name) + (D == 96) * 100
+    q, k, v, do = randn(B, Sq, Hq, D, seed=seed), randn(B, Skv, Hkv, D, seed=seed + 1), randn(B, Skv, Hkv, D, seed=seed + 2), randn(B, Sq, Hq, D, seed=seed + 3)
+    if kind == "exact":
+        q = torch.zeros_like(q)
+        v = (torch.arange(D)[None, :] == (torch.arange(Skv) % D)[:, None]).to(BF)[None, :, None, :].expand(B, Skv, Hkv, D).contiguous()
+    return dict(q=q, k=k, v=v, do=do)
+
+
+def d128_counts(name, D):
+    """-> n [B, Sq] visible keys per row, cnt [B, Sq, D] visible keys j with j % D == d (int64)"""
+    B, Hq, Hkv, Sq, Skv, causal, window, kvl = D128_CASES[name]
+    allow = attention_mask(B, Sq, Skv, causal, kvl, window)[:, 0]
+    onehot = (torch.arange(D)[None, :] == (torch.arange(Skv) % D)[:, None]).long()
+    return allow.sum(-1), allow.long() @ onehot
+
+
+_D128_REFS = {}
+
+
+def d128_refs(name, D, kind):
+    """(inputs, fp64 reference, fp32 reference), computed once per process and left unchanged"""
+    key = (name, D, kind)
+    if key not in _D128_REFS:
+        B, Hq, Hkv, Sq, Skv, causal, window, kvl = D128_CASES[name]
+        inp = d128_inputs(name, D, kind)
+        _D128_REFS[key] = (inp,) + tuple(attention(inp["q"], inp["k"], inp["v"], inp["do"], causal, kvl, window, dt) for dt in (torch.float64, torch.float32))
+    return _D128_REFS[key]
+
+
+def d128_simulate(name, D, kind, mut=None):
+    """what a kernel with fp32 math returns: the fp32 reference (or a mutant of it), o / dq / dk / dv rounded to bf16, lse fp32"""
+    B, Hq, Hkv, Sq, Skv, causal, window, kvl = D128_CASES[name]
+    inp = d128_refs(name, D, kind)[0]
+    out = d128_refs(name, D, kind)[2] if mut is None else attention(inp["q"], inp["k"], inp["v"], inp["do"], causal, kvl, window, torch.float32, mut)
+    return {n: (t.float() if n == "lse" else t.to(BF)) for n, t in out.items()}
+
+
+def _blocks(n, dim):
+    return {f"block{i}": (slice(None),) * dim + (slice(i * D128_BLOCK, min(n, (i + 1) * D128_BLOCK)),) for i in range((n + D128_BLOCK - 1) // D128_BLOCK)}
+
+
+def d128_compare(name, D, kind, got):
+    """The comparisons of tests/test_attention_d128_gpu.py on `got` (o, lse and, if present, dq, dk, dv; CPU tensors).
+    -> (bounded {label: (error, bound)}, exact [what failed]).
+    bounded: lse by absolute error over the non-empty rows per q block, bound the fp32 sum form with n = Skv; o / dq per q block and dk / dv per key
+    block against fp64 with D128_ROUNDINGS, the gradients normalised by the tensor maximum.  exact: everything finite; o, dq zero and
+    lse = EMPTY_LSE on empty rows; dk / dv zero at keys >= kv_len; kind "exact" also round(2^lse) = n, o bit-equal to bf16(cnt / n), dk zero."""
+    B, Hq, Hkv, Sq, Skv, causal, window, kvl = D128_CASES[name]
+    inp, r64, r32 = d128_refs(name, D, kind)
+    n, cnt = d128_counts(name, D)
+    empty = n == 0                                                                     # [B, Sq]
+    res, bad = {}, []
+    for nm, t in got.items():
+        if not bool(torch.isfinite(t.float()).all()):
+            bad.append(f"{nm} is not finite")
+    hide = empty[:, None, :].expand(B, Hq, Sq)
+    lse = got["lse"].float()
+    if not bool((lse[hide] == EMPTY_LSE).all()):
+        bad.append("lse of an empty row is not -1e30")
+    qg3 = _blocks(Sq, 2)
+    want, have = r64["lse"].masked_fill(hide, float("inf")), lse.masked_fill(hide, 0.0)          # group_err leaves non-finite references out
+    y, e = R.group_err(r32["lse"].masked_fill(hide, 0.0), want, qg3, 1.0), R.group_err(have, want, qg3, 1.0)
+    if kind == "random":
+        for g in e:
+            res[f"lse[{g}]"] = (e[g], R.bound(R.out_spec(n=Skv), y[g]))
+    for nm, blocks in (("o", _blocks(Sq, 1)), ("dq", _blocks(Sq, 1)), ("dk", _blocks(Skv, 1)), ("dv", _blocks(Skv, 1))):
+        if nm not in got or (kind == "exact" and nm in ("o", "dk")):
+            continue
+        norm = None if nm == "o" else float(r64[nm].abs().max())
+        y, e = R.group_err(r32[nm], r64[nm], blocks, norm), R.group_err(got[nm], r64[nm], blocks, norm)
+        for g in e:
+            res[f"{nm}[{g}]"] = (e[g], R.bound(R.out_spec(r=D128_ROUNDINGS[nm]), y[g]))
+    for nm in ("o", "dq"):
+        if nm in got and not bool((got[nm].float()[empty] == 0).all()):
+            bad.append(f"{nm} of an empty row is not zero")
+    if kvl is not None:
+        for b, kl in enumerate(kvl):
+            for nm in ("dk", "dv"):
+                if nm in got and kl < Skv and not bool((got[nm][b, kl:].float() == 0).all()):
+                    bad.append(f"{nm} beyond kv_len")
+    if kind == "exact":
+        full = n[:, None, :].expand(B, Hq, Sq)
+        if not bool((torch.round(torch.exp2(lse.double()))[~hide] == full[~hide].double()).all()):
+            bad.append("round(2^lse) is not the number of visible keys")
+        o_want = (cnt.double() / n.clamp_min(1)[..., None].double()).to(BF)[:, :, None, :].expand(B, Sq, Hq, D)
+        if not exact(got["o"], o_want):
+            bad.append("o is not bf16(cnt / n)")
+        if "dk" in got and not bool((got["dk"].float() == 0).all()):
+            bad.append("dk is not zero with q = 0")
+    return res, bad

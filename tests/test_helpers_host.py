@@ -1,10 +1,12 @@
-"""CPU proof behind tests/test_helpers_gpu.py and tests/test_attention_generic_gpu.py.
+"""CPU proof behind tests/test_helpers_gpu.py, tests/test_attention_generic_gpu.py and tests/test_attention_d128_gpu.py.
 
 1. Every reference of tests/helpers_ref.py agrees with torch's own operator where one exists (F.unfold, F.conv_transpose2d with an identity-like
    weight, F.interpolate in both align_corners modes, the oracle's RoPE, index_add_ / plain loops, autograd through attn_ref).
 2. The comparisons used on the GPU (exact / by value / regimes.group_err with its computed bound / close() for attention) accept the honest
    reference evaluated in fp32 with its bf16 output rounding, and reject every mutant of tests/PATHS.md.
-3. Whether TODAY's comparison (close() with the arguments and inputs of tests/test_kernels_gpu.py) sees each mutant: OLD_CATCHES."""
+3. Whether TODAY's comparison (close() with the arguments and inputs of tests/test_kernels_gpu.py) sees each mutant: OLD_CATCHES.
+4. D = 128 / 96 attention at block edges (tests/ATTENTION_D128.md): the reference with lse and defined empty rows against torch's softmax and
+   autograd, the ten mutants against the comparisons of helpers_ref.d128_compare, and the fp32 no-rounding-boundary property of the exact pass."""
 import math
 
 import pytest
@@ -14,6 +16,7 @@ import torch.nn.functional as F
 import helpers_ref as HR
 import regimes as R
 from regimes import BF, gen, randn
+from test_attention_generic_gpu import EDGES
 from test_kernels_gpu import attn_ref, close, rnd
 
 F32, F64 = torch.float32, torch.float64
@@ -184,6 +187,18 @@ OLD_CATCHES = {
     "first sweep only": False,                               # no unit test is large enough for a second sweep
     "attention kv_len ignored in dK / dV": False,            # no backward runs with kv_len at D = 32 / 64
     "attention window lower bound off by one": True,
+    # D = 128: attention_failures with close() on the seven edge shapes of test_attention_d128_dma_kernels_edges (it never looks at lse, no
+    # shape has a causal or windowed row >= 256, an offset past the first block or a row without a key)
+    "d128 block_first_key_dropped": False,
+    "d128 offset_dropped_after_first_block": False,
+    "d128 window_off_by_one": True,
+    "d128 kvlen_ignored_dkdv": True,
+    "d128 empty_row_nan": False,
+    "d128 empty_row_uniform": False,
+    "d128 lse_natural_log": False,
+    "d128 lse_without_last_tile": False,
+    "d128 kv_head_modulo": True,
+    "d128 gqa_last_head_dropped_in_dkdv": True,
 }
 
 
@@ -375,3 +390,97 @@ def test_attention_mutants(D):
         ref = attn_ref(q.float(), k.float(), v.float(), True, window=70)
         assert passes(lambda: close(sim(HR.attention(q, k, v, q, True, None, 70)["o"]), ref))
         assert (not passes(lambda: close(sim(HR.attention(q, k, v, q, True, None, 70, mut="window_off_by_one")["o"]), ref))) == OLD_CATCHES["attention window lower bound off by one"]
+
+
+# ------------------------------------------------------------------------------------------------ D = 128 / 96 at block edges (tests/ATTENTION_D128.md)
+D128 = [(n, D) for n in HR.D128_CASES for D in HR.D128_DIMS]
+
+
+@pytest.mark.parametrize("name,D", D128)
+def test_d128_reference_is_torch_softmax_and_autograd(name, D):
+    """o, lse, dq, dk, dv of helpers_ref.attention in fp64 against torch.softmax / torch.logsumexp and autograd.  torch yields NaN for a row without
+    a visible key, so such rows are given every key here and their output rows multiplied by zero before the backward: what is compared is the
+    non-empty rows, and that an empty row adds nothing."""
+    B, Hq, Hkv, Sq, Skv, causal, window, kvl = HR.D128_CASES[name]
+    inp, ref, _ = HR.d128_refs(name, D, "random")
+    allow = HR.attention_mask(B, Sq, Skv, causal, kvl, window)
+    live = allow.any(-1, keepdim=True)
+    qr, kr, vr = (inp[n].double().requires_grad_(True) for n in ("q", "k", "v"))
+    rep = Hq // Hkv
+    s = qr.transpose(1, 2) @ kr.transpose(1, 2).repeat_interleave(rep, dim=1).transpose(-1, -2) / math.sqrt(D)
+    s = s.masked_fill(~(allow | ~live), float("-inf"))
+    o = ((torch.softmax(s, -1) @ vr.transpose(1, 2).repeat_interleave(rep, dim=1)) * live).transpose(1, 2)
+    o.backward(inp["do"].double())
+    lse = torch.logsumexp(s.detach(), -1) * HR.LOG2E
+    rows = live[:, 0, :, 0]
+    assert int((~rows).sum()) == (407 if name == "window-kvlen-empty" else 0)
+    for nm, want in (("o", o.detach()), ("dq", qr.grad), ("dk", kr.grad), ("dv", vr.grad)):
+        assert float((ref[nm] - want).abs().max()) < 1e-12, nm
+    keep = rows[:, None, :].expand(B, Hq, Sq)
+    assert float((ref["lse"] - lse)[keep].abs().max()) < 1e-12
+    assert bool((ref["lse"][~keep] == HR.EMPTY_LSE).all()) and bool((ref["o"][~rows] == 0).all()) and bool((ref["dq"][~rows] == 0).all())
+
+
+def _rejected(name, D, kind, mut):
+    res, bad = HR.d128_compare(name, D, kind, HR.d128_simulate(name, D, kind, mut))
+    return [k for k, (e, b) in res.items() if not e <= b], bad
+
+
+@pytest.mark.parametrize("name,D", D128)
+def test_d128_comparisons_accept_the_honest_reference(name, D):
+    for kind in ("random", "exact"):
+        assert _rejected(name, D, kind, None) == ([], []), kind
+
+
+@pytest.mark.parametrize("D", HR.D128_DIMS)
+@pytest.mark.parametrize("mut", HR.ATTENTION_MUTANTS)
+def test_d128_mutants(mut, D):
+    """the comparisons of tests/test_attention_d128_gpu.py reject each mutant on the case it is aimed at, in the random AND in the exact pass"""
+    name = HR.D128_MUTANT_CASE[mut]
+    (bounded, exact), (bounded_x, exact_x) = _rejected(name, D, "random", mut), _rejected(name, D, "exact", mut)
+    assert bounded or exact, "random pass"
+    assert bounded_x or exact_x, "exact pass"
+    if mut in ("block_first_key_dropped", "offset_dropped_after_first_block", "window_off_by_one", "lse_natural_log", "lse_without_last_tile"):
+        assert any(g.startswith("lse") for g in bounded) and "round(2^lse) is not the number of visible keys" in exact_x
+    if mut in ("block_first_key_dropped", "offset_dropped_after_first_block", "window_off_by_one"):
+        assert "o is not bf16(cnt / n)" in exact_x
+    if mut.startswith("empty_row"):
+        assert {"lse of an empty row is not -1e30", "o of an empty row is not zero", "dq of an empty row is not zero"} <= set(exact)
+    if mut == "kvlen_ignored_dkdv":
+        assert {"dk beyond kv_len", "dv beyond kv_len"} <= set(exact)
+    if mut == "block_first_key_dropped":
+        # with equal scores (the exact pass) every row that loses key 256 moves its lse by log2(n / (n - 1)) >= 1 / (513 ln 2) = 2.8e-3, eighty times
+        # the lse bound; with N(0, 1) scores the lost key's weight varies from row to row, and it is the block's largest move that is compared
+        got, ref = HR.d128_simulate(name, D, "exact", mut)["lse"], HR.d128_refs(name, D, "exact")[1]["lse"]
+        assert float((got.double() - ref)[:, :, 256:].abs().min()) >= 2.8e-3
+        assert {"lse[block1]", "lse[block2]"} <= set(bounded)
+
+
+def test_d128_old_catches():
+    """the parent's comparison (attention_failures with close() on the seven edge shapes, D = 128) on the ten mutants: OLD_CATCHES"""
+    D = 128
+    old = {m: False for m in HR.ATTENTION_MUTANTS}
+    for (B, Hq, Hkv, Sq, Skv, causal, window, kvl) in EDGES:
+        q, k, v, do = rnd(B, Sq, Hq, D, seed=81), rnd(B, Skv, Hkv, D, seed=82), rnd(B, Skv, Hkv, D, seed=83), rnd(B, Sq, Hq, D, seed=84)
+        ref = HR.attention(q, k, v, do, causal, kvl, window)
+        assert not HR.attention_failures({n_: sim(t) for n_, t in ref.items()}, ref, kvl, close)
+        for m in old:
+            got = {n_: sim(t) for n_, t in HR.attention(q, k, v, do, causal, kvl, window, mut=m).items()}
+            old[m] |= bool(HR.attention_failures(got, ref, kvl, close))
+    assert old == {m: OLD_CATCHES[f"d128 {m}"] for m in HR.ATTENTION_MUTANTS}
+    assert sum(old.values()) == 4
+
+
+@pytest.mark.parametrize("name,D", D128)
+def test_d128_exact_pass_is_out_of_reach_of_a_rounding_boundary(name, D):
+    """The exact pass demands o == bf16(cnt / n) bit for bit.  A kernel forms it in fp32 as cnt * (1 / n), its reciprocal possibly a hardware
+    approximation: for every row of every case cnt * fp32(1 / n) rounds to the same bf16 as the fp64 quotient, also with 1 / n off by +-2^-22
+    relative (four fp32 ulps)."""
+    n, cnt = HR.d128_counts(name, D)
+    live = n > 0
+    n, cnt = n[live], cnt[live]
+    assert int(cnt.max()) <= 8 and bool((cnt.sum(-1) == n).all())
+    want = (cnt.double() / n.double()[:, None]).to(BF)
+    for pert in (0.0, 2.0 ** -22, -2.0 ** -22):
+        inv = ((1.0 / n.double()).float().double() * (1.0 + pert)).float()
+        assert HR.exact((cnt.float() * inv[:, None]).to(BF), want), pert
