@@ -2,8 +2,8 @@
 tests/test_decode_edges_gpu.py.  Importable without a device and without the built library.  tests/DECODE_PATHS.md maps every path to its case.
 
   chunk_paths    a Python model of what each wave of a skinny-GEMM block sees for a (K, ks): idle, a whole or partial first chunk, and per
-                 step (whole | partial, NEXT 0 | 1 | 2, the wave's first | second | third chunk).  ksplit restates dg_ksplit / dg8_ksplit /
-                 dg4_ksplit; the GPU test holds it against the library's workspace query.
+                 step (whole | partial, NEXT 0 | 1 | 2, the wave's first | second | third chunk).  ksplit restates dg_ksplit with each
+                 format's chunk; the GPU test holds it against the library's workspace query.
   gemm_inputs    exact-valued operands: A in {-1, 0, 1}, weights that every format holds (integers times power-of-two row scales, or e2m1
                  values times power-of-two block scales), integer residuals.  Every partial sum is a multiple of 2^-4 below 2^20, which the
                  generator asserts from the fp64 products: fp32 accumulation is then exact in any order and under any split, and every

@@ -101,7 +101,7 @@ def test_gemm_sumsq_rstd_regimes(ops):
 @pytest.mark.parametrize("H", [64, 1024, 4096])
 @pytest.mark.parametrize("M", [1, 14])
 def test_decode_gemm_norm_prologue_regimes(ops, H, M):
-    """vp_decode_gemm's RMSNorm prologue on the regime rows: the normalised A must be vp_rmsnorm_fwd's (decode.hip:74 claims its rstd bit-identical;
+    """vp_decode_gemm's RMSNorm prologue on the regime rows: the normalised A must be vp_rmsnorm_fwd's (decode.hip's dg_rstd_rows claims its rstd bit-identical;
     test_rmsnorm_regimes holds that kernel to fp64), so the fp32 product is compared with fp64 `rmsnorm_fwd(x) @ w^T`: r = 0, sums K = H terms."""
     inp = R.rmsnorm_inputs(H)
     x, kinds = inp.x[-M:], inp.kinds[-M:]                        # M = 1: the spike row; M = 14: every regime
@@ -211,7 +211,7 @@ def test_gemm_swiglu_fused_regimes(ops, M, Fd, K):
 
 @pytest.mark.parametrize("il", [True, False])
 def test_decode_gemm_swiglu_epilogue_regimes(ops, il):
-    """vp_decode_gemm's SwiGLU epilogue (decode.hip:56-57: bf16(bf16(silu(bf16(gate))) * bf16(up))) with one-hot A rows: r = 2."""
+    """vp_decode_gemm's SwiGLU epilogue (decode.hip's dg_store: bf16(bf16(silu(bf16(gate))) * bf16(up))) with one-hot A rows: r = 2."""
     inp = R.swiglu_inputs()
     Fd, K, M = inp.Fd, 64, 8
     pat = torch.cat([inp.gate, inp.up], 1)

@@ -155,7 +155,7 @@ def test_w4_kernels_use_no_scratch_and_do_not_spill():
     import kernel_resources as kr
     so = os.path.join(os.path.dirname(__file__), "..", "visper-lm_amd", "libvisper_hip.so")
     assert os.path.exists(so), "library not built"
-    res = kr.matching(so, ("decode_gemm_w4_kernel", "decode_gemm_w4_combine_kernel", "quant_blocks_mxfp4_kernel"))
+    res = kr.matching(so, ("decode_gemm_w4_kernel", "decode_gemm_combine_kernel", "quant_blocks_mxfp4_kernel"))
     assert len(res) == 4, sorted(res)                                 # <true> / <false> norm prologue, the combine, the quantiser
     for n, d in res.items():
         assert d.get("private_segment_fixed_size", 0) == 0 and d.get("vgpr_spill_count", 0) == 0 and d.get("sgpr_spill_count", 0) == 0, (n, d)

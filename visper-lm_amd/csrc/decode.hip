@@ -1,15 +1,18 @@
 // Single-token decode kernels (KV-cached generation): the reference generates with HF's generation loop over `inputs_embeds`
 // (base_ola_vlm.py:579-616, llava_llama.py:122; called by eval/model_cvbench_loader.py:127, model_mmstar_loader.py:125, demo.py:328).
 // At one token per sequence every decoder GEMM has M = B <= 16 rows and is bound by the bytes of its weight, not by MFMA work:
-//  - decode_gemm_kernel: C[M,N] = epi(A[M,K] W[N,K]^T), W streamed once straight into VGPRs (no LDS round trip), one 16-row W tile per
-//    block, the K range split over the block's 4 waves (and, where N has too few tiles to fill the chip, over KS blocks: fp32 slabs in a
-//    caller-owned workspace, summed in a fixed order by decode_gemm_combine_kernel).  Optional RMSNorm prologue (rstd of the <= 16 A rows
-//    computed by every block, gamma applied while A is loaded: vp_rmsnorm_fwd's rounding points), epilogues: none (bf16 / fp32 out),
-//    + residual, SwiGLU (act written directly).
-//  - decode_rope_append_kernel: rotate-half RoPE of q / k at per-sequence positions pos[b] (vp_rope's rounding points), k / v appended
-//    to row pos[b] of the cache.
-//  - decode_attn_split_kernel + decode_attn_combine_kernel: one query row per sequence, the Hq/Hkv heads of a KV head share every
-//    K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
+//  - decode_gemm_kernel / decode_gemm_w8_kernel / decode_gemm_w4_kernel (bf16 | e4m3 rows | MXFP4 blocks of W): C[M,N] = epi(A[M,K] W[N,K]^T),
+//    W streamed once straight into VGPRs (no LDS round trip), one 16-row W tile per block, the K range split over the block's 4 waves (and,
+//    where N has too few tiles to fill the chip, over KS blocks: fp32 slabs in a caller-owned workspace, summed in a fixed order by
+//    decode_gemm_combine_kernel).  Optional RMSNorm prologue (rstd of the <= 16 A rows computed by every block, gamma applied while A is
+//    loaded: vp_rmsnorm_fwd's rounding points), epilogues: none (bf16 / fp32 out), + residual, SwiGLU (act written directly).  Each format
+//    owns its chunk loop (hand-shaped loads, waits and registers); argument block, split rule, prologue, reduction, epilogue, combine and
+//    the host side (dg_run) are one piece of code for the three.
+//  - decode_rope_append_kernel / decode_rope_append_kv8_kernel: rotate-half RoPE of q / k at per-sequence positions pos[b] (vp_rope's
+//    rounding points), k / v appended to row pos[b] of the bf16 | e4m3 cache.
+//  - decode_attn_split_kernel / decode_attn_split_kv8_kernel + decode_attn_combine_kernel: one query row per sequence, the Hq/Hkv heads of
+//    a KV head share every K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
+//  - the quantisers that make the byte operands: quant_rows_e4m3_kernel, quant_blocks_mxfp4_kernel, quant_kv_e4m3_kernel.
 #include "common.h"
 #include "fp8_e4m3.h"
 #include "mxfp4.h"
@@ -22,19 +25,24 @@ static constexpr int DG_THREADS = 256;       // 4 waves
 static constexpr int DG_KCHUNK = 256;        // K elements one wave consumes per iteration: 4 lane groups x 64
 static constexpr int DG_TARGET_BLOCKS = 512; // grid the K split aims for (2 blocks per CU on 256 CUs)
 
+// one argument block for the three weight formats: W = bf16 rows | e4m3fn bytes | packed e2m1 codes (ldw in elements | bytes | bytes)
 struct DecGemmArgs {
   const bf16_t* A; const bf16_t* W; void* C; const bf16_t* res; const bf16_t* gamma;
   float* ws;
   int M, N, K, Kc, epi, out_f32, KS;
   long lda, ldw, ldc, ldr;
   float eps;
+  const float* wscale;                       // W8: one fp32 scale per W row; null otherwise
+  const uint8_t* E;                          // W4: e8m0 scale bytes [N, K / 32], row stride lde; null / 0 otherwise
+  long lde;
 };
 
-// split-K factor: a pure function of the shape (the workspace size query and the launch agree; results do not depend on the device)
-static int dg_ksplit(int N, int K, int epi) {
+// split-K factor: a pure function of the shape and of the format's chunk (K elements one wave consumes per iteration), so the workspace
+// size query and the launch agree and results do not depend on the device
+static int dg_ksplit(int N, int K, int epi, int kchunk) {
   const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
   int ks = 1;
-  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG_KCHUNK) == 0) ks *= 2;
+  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * kchunk) == 0) ks *= 2;
   return ks;
 }
 
@@ -64,6 +72,58 @@ __device__ __forceinline__ void dg_store(const DecGemmArgs& p, int m, int n, flo
   ((bf16_t*)p.C)[(long)m * p.ldc + n] = f2bf(v);
 }
 
+// rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical); wave w takes
+// rows w, w + 4, ...; ends with the block's barrier
+__device__ __forceinline__ void dg_rstd_rows(const DecGemmArgs& p, int w, int lane, float* rstd_s) {
+  for (int mm = w; mm < p.M; mm += 4) {
+    const bf16_t* a2 = p.A + (long)mm * p.lda;
+    float ss = 0.f;
+    for (int e = lane * 8; e < p.K; e += 512) {
+      const bf16x8 v = *(const bf16x8*)(a2 + e);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) rstd_s[mm] = rsqrtf(ss / (float)p.K + p.eps);
+  }
+  __syncthreads();
+}
+
+// the 4 waves' accumulators -> one 16 x 16 tile in a fixed order, then the fp32 slab of split ks (KS > 1: unscaled) or the epilogue.
+// ROWSCALE (W8): W row n's sum is multiplied by wscale[n] before dg_store's first rounding point
+template <bool ROWSCALE>
+__device__ __forceinline__ void dg_reduce_store(const DecGemmArgs& p, f32x4 acc, int t, int ks, int w, int lane, float (*red)[256],
+                                                float (*tile_s)[17]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
+  __syncthreads();
+  {
+    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
+    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
+  }
+  __syncthreads();
+  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
+    const int nn = dg_row(p, t, nl);
+    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
+    return;
+  }
+  if (p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES) {
+    if (threadIdx.x < 128 && mm < p.M) {
+      float v = tile_s[nl][mm], u = tile_s[nl + 8][mm];
+      if (ROWSCALE) { v *= p.wscale[dg_row(p, t, nl)]; u *= p.wscale[dg_row(p, t, nl + 8)]; }
+      dg_store(p, mm, 8 * t + nl, v, u);
+    }
+    return;
+  }
+  if (mm < p.M && 16 * t + nl < p.N) {
+    float v = tile_s[nl][mm];
+    if (ROWSCALE) v *= p.wscale[16 * t + nl];
+    dg_store(p, mm, 16 * t + nl, v, 0.f);
+  }
+}
+
 template <bool NORM>
 __global__ __launch_bounds__(DG_THREADS) void decode_gemm_kernel(DecGemmArgs p) {
   __shared__ float red[4][256];
@@ -72,21 +132,7 @@ __global__ __launch_bounds__(DG_THREADS) void decode_gemm_kernel(DecGemmArgs p) 
   const int t = blockIdx.x, ks = blockIdx.y;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
-  if (NORM) {
-    // rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical)
-    for (int m = w; m < p.M; m += 4) {
-      const bf16_t* ar = p.A + (long)m * p.lda;
-      float ss = 0.f;
-      for (int e = lane * 8; e < p.K; e += 512) {
-        const bf16x8 v = *(const bf16x8*)(ar + e);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
-      }
-      ss = wave_sum(ss);
-      if (lane == 0) rstd_s[m] = rsqrtf(ss / (float)p.K + p.eps);
-    }
-    __syncthreads();
-  }
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
   // rows past N / M are clamped to the last valid row: their results are never stored, so the hot loop needs no masks
   const int n = min(dg_row(p, t, r), p.N - 1);
   const int m = min(r, p.M - 1);
@@ -121,35 +167,11 @@ __global__ __launch_bounds__(DG_THREADS) void decode_gemm_kernel(DecGemmArgs p) 
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[u], av[u], acc, 0, 0, 0);
     }
   }
-  // 4 waves -> one 16 x 16 tile, fixed order
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
-  __syncthreads();
-  {
-    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
-    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
-    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
-  }
-  __syncthreads();
-  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
-  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
-    const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
-    const int nn = dg_row(p, t, nl);
-    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
-    return;
-  }
-  if (swiglu) {
-    if (threadIdx.x < 128) {
-      const int j = threadIdx.x >> 4, mm = threadIdx.x & 15;
-      if (mm < p.M) dg_store(p, mm, 8 * t + j, tile_s[j][mm], tile_s[j + 8][mm]);
-    }
-    return;
-  }
-  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
-  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm], 0.f);
+  dg_reduce_store<false>(p, acc, t, ks, w, lane, red, tile_s);
 }
 
-// sums the KS slabs in order and applies the epilogue; one thread per output element
+// all three formats: sums the KS slabs in order, scales by the row's weight scale where there is one (W8) and applies the epilogue; one
+// thread per output element
 __global__ __launch_bounds__(256) void decode_gemm_combine_kernel(DecGemmArgs p) {
   const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
   const int nout = swiglu ? p.N / 2 : p.N;
@@ -162,12 +184,13 @@ __global__ __launch_bounds__(256) void decode_gemm_combine_kernel(DecGemmArgs p)
     const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
     float v = 0.f, u = 0.f;
     for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
+    if (p.wscale) { v *= p.wscale[rg]; u *= p.wscale[ru]; }
     dg_store(p, m, n, v, u);
     return;
   }
   float v = 0.f;
   for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
-  dg_store(p, m, n, v, 0.f);
+  dg_store(p, m, n, p.wscale ? v * p.wscale[n] : v, 0.f);
 }
 
 // ---------------------------------------------------------------- FP8 weight-only decode ---------------
@@ -175,11 +198,32 @@ __global__ __launch_bounds__(256) void decode_gemm_combine_kernel(DecGemmArgs p)
 // gfx950's native answer is OCP e4m3fn weights with one power-of-two fp32 scale per row (fp8_e4m3.h, quant.py: the contract), converted
 // exactly to bf16 in registers: a 16-byte load then carries 16 weights instead of 8 and the skinny GEMM streams half the bytes.
 //  - quant_rows_e4m3_kernel: one block per row: absmax -> scale -> bytes (+ the dequantised value written back over the bf16 row).
-//  - decode_gemm_w8_kernel: decode_gemm_kernel's structure (one 16-row W tile per block, K over the 4 waves and KS blocks, the same MFMA with
-//    the same k permutation on both operands, the same prologue / epilogues through dg_norm / dg_store); a wave consumes 512 k per chunk =
+//  - decode_gemm_w8_kernel: one 16-row W tile per block, K over the 4 waves and KS blocks, the bf16 kernel's MFMA with the same k
+//    permutation on both operands, the shared prologue / epilogue (dg_rstd_rows, dg_norm, dg_reduce_store); a wave consumes 512 k per chunk =
 //    8 loads of 16 fp8 per lane, each feeding two MFMAs.  The next chunk's 8 loads are issued before the current chunk is converted, and
 //    the first chunk's before the rstd pass of the norm prologue, so the conversion (one v_cvt_scalef32_pk_bf16_fp8 per pair) never waits
 //    with no load in flight.  Row n's fp32 sum is multiplied by w_scale[n] before the epilogue's first rounding point.
+
+// the two halves of the e4m3 row contract on one 8-wide vector (weight rows here, KV heads below): the running absmax of the bf16 magnitudes ...
+__device__ __forceinline__ uint32_t e4m3_absmax8(const bf16x8 v, uint32_t am) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[j] & 0x7fffu);
+  return am;
+}
+
+// ... and 8 bf16 -> 8 e4m3fn bytes of v / 2^se and their dequantised values
+__device__ __forceinline__ void e4m3_quant8(const bf16x8 v, int se, u32x2& q, bf16x8& d) {
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t b = vp_e4m3_quant((uint16_t)v[j], se);
+    if (j < 4) lo |= b << (8 * j); else hi |= b << (8 * (j - 4));
+    d[j] = (short)vp_e4m3_dequant_bf16(b, se);
+  }
+  q[0] = lo;
+  q[1] = hi;
+}
+
 __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(bf16_t* __restrict__ W, long ldw, uint8_t* __restrict__ Q, long ldq,
                                                               float* __restrict__ scale, int K, int writeback) {
   __shared__ uint32_t red[4];
@@ -187,11 +231,7 @@ __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(bf16_t* __restrict
   bf16_t* wr = W + n * ldw;
   uint8_t* qr = Q + n * ldq;
   uint32_t am = 0;
-  for (int k = threadIdx.x * 8; k < K; k += 256 * 8) {
-    const bf16x8 v = *(const bf16x8*)(wr + k);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[j] & 0x7fffu);
-  }
+  for (int k = threadIdx.x * 8; k < K; k += 256 * 8) am = e4m3_absmax8(*(const bf16x8*)(wr + k), am);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
@@ -200,34 +240,15 @@ __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(bf16_t* __restrict
   const int se = vp_e4m3_scale_exp(am);
   if (threadIdx.x == 0) scale[n] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
   for (int k = threadIdx.x * 8; k < K; k += 256 * 8) {
-    const bf16x8 v = *(const bf16x8*)(wr + k);
+    u32x2 qv;
     bf16x8 d;
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t q = vp_e4m3_quant((uint16_t)v[j], se);
-      if (j < 4) lo |= q << (8 * j); else hi |= q << (8 * (j - 4));
-      d[j] = (short)vp_e4m3_dequant_bf16(q, se);
-    }
-    const u32x2 qv = {lo, hi};
+    e4m3_quant8(*(const bf16x8*)(wr + k), se, qv, d);
     *(u32x2*)(qr + k) = qv;
     if (writeback) *(bf16x8*)(wr + k) = d;
   }
 }
 
 static constexpr int DG8_KCHUNK = 512;       // K elements one wave consumes per iteration: 8 loads x 4 lane groups x 16 fp8
-
-struct DecGemmW8Args {
-  DecGemmArgs g;                             // g.W = the fp8 bytes, g.ldw in bytes
-  const float* wscale;
-};
-
-static int dg8_ksplit(int N, int K, int epi) {
-  const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
-  int ks = 1;
-  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG8_KCHUNK) == 0) ks *= 2;
-  return ks;
-}
 
 // 16 e4m3fn bytes -> two MFMA fragments (bytes 0..7 | bytes 8..15), exact.  gfx950 converts a pair of fp8 straight to a bf16 pair
 // (v_cvt_scalef32_pk_bf16_fp8 with scale 1: one instruction per two weights)
@@ -305,11 +326,10 @@ __device__ __forceinline__ f32x4 dg8_chunk(f32x4 acc, const u32x4* wq, u32x4* wn
 }
 
 template <bool NORM>
-__global__ __launch_bounds__(DG_THREADS, 3) void decode_gemm_w8_kernel(DecGemmW8Args q) {
+__global__ __launch_bounds__(DG_THREADS, 3) void decode_gemm_w8_kernel(DecGemmArgs p) {
   __shared__ float red[4][256];
   __shared__ float tile_s[16][17];
   __shared__ float rstd_s[16];
-  const DecGemmArgs& p = q.g;
   const int t = blockIdx.x, ks = blockIdx.y;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
@@ -322,21 +342,7 @@ __global__ __launch_bounds__(DG_THREADS, 3) void decode_gemm_w8_kernel(DecGemmW8
   int c = kbeg + w * DG8_KCHUNK;
   u32x4 w0[8], w1[8];                                            // ping-pong: one chunk converts while the next one streams
   if (c < kend) dg8_load<8>(w0, wr, c + g * 16, kend, c + DG8_KCHUNK <= kend);       // the first chunk is in flight under the rstd pass
-  if (NORM) {
-    // rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical)
-    for (int mm = w; mm < p.M; mm += 4) {
-      const bf16_t* a2 = p.A + (long)mm * p.lda;
-      float ss = 0.f;
-      for (int e = lane * 8; e < p.K; e += 512) {
-        const bf16x8 v = *(const bf16x8*)(a2 + e);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
-      }
-      ss = wave_sum(ss);
-      if (lane == 0) rstd_s[mm] = rsqrtf(ss / (float)p.K + p.eps);
-    }
-    __syncthreads();
-  }
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
   const float rs = NORM ? rstd_s[m] : 1.f;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #define DG8_STEP(WQ, WN)                                                                                          \
@@ -354,55 +360,7 @@ __global__ __launch_bounds__(DG_THREADS, 3) void decode_gemm_w8_kernel(DecGemmW8
     DG8_STEP(w1, w0)
   }
 #undef DG8_STEP
-  // 4 waves -> one 16 x 16 tile, fixed order
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
-  __syncthreads();
-  {
-    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
-    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
-    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
-  }
-  __syncthreads();
-  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
-  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order, unscaled), summed by the combine kernel
-    const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
-    const int nn = dg_row(p, t, nl);
-    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
-    return;
-  }
-  if (swiglu) {
-    if (threadIdx.x < 128) {
-      const int j = threadIdx.x >> 4, mm = threadIdx.x & 15;
-      if (mm < p.M)
-        dg_store(p, mm, 8 * t + j, tile_s[j][mm] * q.wscale[dg_row(p, t, j)], tile_s[j + 8][mm] * q.wscale[dg_row(p, t, j + 8)]);
-    }
-    return;
-  }
-  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
-  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm] * q.wscale[16 * t + nl], 0.f);
-}
-
-// sums the KS slabs in order, scales by the row's weight scale and applies the epilogue; one thread per output element
-__global__ __launch_bounds__(256) void decode_gemm_w8_combine_kernel(DecGemmW8Args q) {
-  const DecGemmArgs& p = q.g;
-  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
-  const int nout = swiglu ? p.N / 2 : p.N;
-  const long i = blockIdx.x * 256L + threadIdx.x;
-  if (i >= (long)p.M * nout) return;
-  const int m = (int)(i / nout), n = (int)(i % nout);
-  const long slab = (long)p.M * p.N;
-  if (swiglu) {
-    const int t = n >> 3, j = n & 7;
-    const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
-    float v = 0.f, u = 0.f;
-    for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
-    dg_store(p, m, n, v * q.wscale[rg], u * q.wscale[ru]);
-    return;
-  }
-  float v = 0.f;
-  for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
-  dg_store(p, m, n, v * q.wscale[n], 0.f);
+  dg_reduce_store<true>(p, acc, t, ks, w, lane, red, tile_s);
 }
 
 // ---------------------------------------------------------------- MXFP4 weight-only decode ---------------
@@ -411,11 +369,11 @@ __global__ __launch_bounds__(256) void decode_gemm_w8_combine_kernel(DecGemmW8Ar
 // (v_cvt_scalef32_pk_bf16_fp4, exact: a 2-bit significand times a power of two), so a 16-byte load carries 32 weights = one scale block.
 //  - quant_blocks_mxfp4_kernel: one thread per block of 32 k: absmax -> scale byte -> 16 bytes of codes (+ the dequantised value written back
 //    over the bf16 block), integer arithmetic only.
-//  - decode_gemm_w4_kernel: decode_gemm_w8_kernel's structure (one 16-row W tile per block, K over the 4 waves and KS blocks, the same MFMA
-//    with the same k permutation on both operands, dg_norm / dg_store); a wave consumes 512 k per chunk = 4 loads of 32 codes per lane, each
-//    feeding four MFMAs.  The chunk's 16 scale bytes of a row come in one 16-byte load per lane, issued with the weight loads (lane group g
-//    uses byte g of word u for load u), so no weight load waits for a scale.  The next chunk's loads are issued before the current chunk is
-//    converted, the first chunk's before the rstd pass.  The scale is part of the converted value: the epilogue has no per-row multiply.
+//  - decode_gemm_w4_kernel: the same tile, K split, MFMA, k permutation and shared prologue / epilogue as the two kernels above (no row
+//    scale in dg_reduce_store); a wave consumes 512 k per chunk = 4 loads of 32 codes per lane, each feeding four MFMAs.  The chunk's 16
+//    scale bytes of a row come in one 16-byte load per lane, issued with the weight loads (lane group g uses byte g of word u for load u),
+//    so no weight load waits for a scale.  The next chunk's loads are issued before the current chunk is converted, the first chunk's
+//    before the rstd pass.  The scale is part of the converted value: the epilogue has no per-row multiply.
 __global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(bf16_t* __restrict__ W, long ldw, uint8_t* __restrict__ Q, long ldq,
                                                                  uint8_t* __restrict__ E, long lde, int N, int K, int writeback) {
   const int nb = K / VP_MXFP4_BLOCK;
@@ -451,22 +409,10 @@ __global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(bf16_t* __restr
   *(u32x4*)(Q + n * ldq + b * 16) = qv;
 }
 
-static constexpr int DG4_KCHUNK = 512;       // K elements one wave consumes per iteration: 4 loads x 4 lane groups x 32 codes (16 scale blocks)
+// K elements one wave consumes per iteration: 4 loads x 4 lane groups x 32 codes (16 scale blocks).  A 512-k chunk per wave (not 1024)
+// leaves K = 4096 two chunk rounds of the 4 waves, so split-K can still halve it
+static constexpr int DG4_KCHUNK = 512;
 static constexpr int DG4_LOADS = 4;
-
-struct DecGemmW4Args {
-  DecGemmArgs g;                             // g.W = the packed codes, g.ldw in bytes
-  const uint8_t* E;                          // e8m0 scale bytes [N, K / 32]
-  long lde;
-};
-
-// a 512-k chunk per wave (not 1024) leaves K = 4096 two chunk rounds of the 4 waves, so split-K can still halve it
-static int dg4_ksplit(int N, int K, int epi) {
-  const int tiles = (epi == VP_EPI_SWIGLU_IL || epi == VP_EPI_SWIGLU_HALVES) ? N / 16 : (N + 15) / 16;
-  int ks = 1;
-  while (tiles * ks < DG_TARGET_BLOCKS && ks < 8 && K % (2 * ks * DG4_KCHUNK) == 0) ks *= 2;
-  return ks;
-}
 
 // 8 e2m1 codes (one 32-bit word: k .. k + 7) times the block scale -> one MFMA fragment, exact.  One instruction per two weights; its last
 // operand selects the byte of the word
@@ -552,54 +498,11 @@ __device__ __forceinline__ f32x4 dg4_chunk(f32x4 acc, const u32x4* wq, const u32
   return acc;
 }
 
-// rstd of every A row over the WHOLE K (same lane -> element assignment and summation order as vp_rmsnorm_fwd: bit-identical); wave w takes
-// rows w, w + 4, ...; ends with the block's barrier
-__device__ __forceinline__ void dg_rstd_rows(const DecGemmArgs& p, int w, int lane, float* rstd_s) {
-  for (int mm = w; mm < p.M; mm += 4) {
-    const bf16_t* a2 = p.A + (long)mm * p.lda;
-    float ss = 0.f;
-    for (int e = lane * 8; e < p.K; e += 512) {
-      const bf16x8 v = *(const bf16x8*)(a2 + e);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float f = bf2f((bf16_t)v[j]); ss += f * f; }
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) rstd_s[mm] = rsqrtf(ss / (float)p.K + p.eps);
-  }
-  __syncthreads();
-}
-
-// the 4 waves' accumulators -> one 16 x 16 tile in a fixed order, then the fp32 slab of split ks (KS > 1) or the epilogue (no row scale)
-__device__ __forceinline__ void dg_reduce_store(const DecGemmArgs& p, f32x4 acc, int t, int ks, int w, int lane, float (*red)[256],
-                                                float (*tile_s)[17]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][lane * 4 + i] = acc[i];
-  __syncthreads();
-  {
-    const int idx = threadIdx.x, l2 = idx >> 2, i = idx & 3;
-    const float s = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
-    tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
-  }
-  __syncthreads();
-  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
-  if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
-    const int nn = dg_row(p, t, nl);
-    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
-    return;
-  }
-  if (p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES) {
-    if (threadIdx.x < 128 && mm < p.M) dg_store(p, mm, 8 * t + nl, tile_s[nl][mm], tile_s[nl + 8][mm]);
-    return;
-  }
-  if (mm < p.M && 16 * t + nl < p.N) dg_store(p, mm, 16 * t + nl, tile_s[nl][mm], 0.f);
-}
-
 template <bool NORM>
-__global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmW4Args q) {
+__global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmArgs p) {
   __shared__ float red[4][256];
   __shared__ float tile_s[16][17];
   __shared__ float rstd_s[16];
-  const DecGemmArgs& p = q.g;
   const int t = blockIdx.x, ks = blockIdx.y;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
@@ -607,11 +510,11 @@ __global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmW4
   const int n = min(dg_row(p, t, r), p.N - 1);
   const int m = min(r, p.M - 1);
   const uint8_t* wr = (const uint8_t*)p.W + (long)n * p.ldw;
-  const uint8_t* er = q.E + (long)n * q.lde;
+  const uint8_t* er = p.E + (long)n * p.lde;
   const bf16_t* ar = p.A + (long)m * p.lda;
   const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
   // every row's scale bytes 16-byte aligned (block-uniform): whole chunks fetch their 16 scale bytes in one load
-  const bool evec = ((((uintptr_t)q.E) | (uintptr_t)q.lde) & 15) == 0;
+  const bool evec = ((((uintptr_t)p.E) | (uintptr_t)p.lde) & 15) == 0;
   int c = kbeg + w * DG4_KCHUNK;
   u32x4 w0[DG4_LOADS], w1[DG4_LOADS], s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};  // ping-pong: one chunk converts while the next one streams
   if (c < kend) {                                                // the first chunk is in flight under the rstd pass
@@ -638,31 +541,20 @@ __global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmW4
     DG4_STEP(w1, s1, w0, s0)
   }
 #undef DG4_STEP
-  dg_reduce_store(p, acc, t, ks, w, lane, red, tile_s);
-}
-
-// sums the KS slabs in order and applies the epilogue (the scales are already in the sums); one thread per output element
-__global__ __launch_bounds__(256) void decode_gemm_w4_combine_kernel(DecGemmArgs p) {
-  const bool swiglu = p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES;
-  const int nout = swiglu ? p.N / 2 : p.N;
-  const long i = blockIdx.x * 256L + threadIdx.x;
-  if (i >= (long)p.M * nout) return;
-  const int m = (int)(i / nout), n = (int)(i % nout);
-  const long slab = (long)p.M * p.N;
-  if (swiglu) {
-    const int t = n >> 3, j = n & 7;
-    const int rg = dg_row(p, t, j), ru = dg_row(p, t, j + 8);
-    float v = 0.f, u = 0.f;
-    for (int k = 0; k < p.KS; ++k) { v += p.ws[k * slab + (long)m * p.N + rg]; u += p.ws[k * slab + (long)m * p.N + ru]; }
-    dg_store(p, m, n, v, u);
-    return;
-  }
-  float v = 0.f;
-  for (int k = 0; k < p.KS; ++k) v += p.ws[k * slab + (long)m * p.N + n];
-  dg_store(p, m, n, v, 0.f);
+  dg_reduce_store<false>(p, acc, t, ks, w, lane, red, tile_s);
 }
 
 // ---------------------------------------------------------------- RoPE + KV append ---------------
+// rotate-half RoPE of 8 element pairs (a: the head's first half, b: its partner in the second half) by 8 table entries: vp_rope's rounding points
+__device__ __forceinline__ void rope_rot8(const bf16x8 a, const bf16x8 b, const float* c, const float* s, bf16x8& oa, bf16x8& ob) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float x1 = bf2f((bf16_t)a[j]), x2 = bf2f((bf16_t)b[j]);
+    oa[j] = (short)f2bf(bfround(x1 * c[j]) + bfround(-x2 * s[j]));
+    ob[j] = (short)f2bf(bfround(x2 * c[j]) + bfround(x1 * s[j]));
+  }
+}
+
 // qkv [B, ldq] rows (q heads | k heads | v heads); thread = one 8-wide vector of one head's first half (q / k) or 16 elements of v
 __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo, long ldq,
                                           bf16_t* __restrict__ kc, long k_bs, long k_ts, bf16_t* __restrict__ vc, long v_bs, long v_ts,
@@ -682,15 +574,8 @@ __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long l
       const bf16_t* src = row + (long)h * D + v * 8;
       const bf16x8 a = *(const bf16x8*)src, bb = *(const bf16x8*)(src + half);
       const int pc = min(max(p, 0), Smax - 1);
-      const float* c = cs + (long)pc * half + v * 8;
-      const float* s = sn + (long)pc * half + v * 8;
       bf16x8 oa, ob;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float x1 = bf2f((bf16_t)a[j]), x2 = bf2f((bf16_t)bb[j]);
-        oa[j] = (short)f2bf(bfround(x1 * c[j]) + bfround(-x2 * s[j]));
-        ob[j] = (short)f2bf(bfround(x2 * c[j]) + bfround(x1 * s[j]));
-      }
+      rope_rot8(a, bb, cs + (long)pc * half + v * 8, sn + (long)pc * half + v * 8, oa, ob);
       bf16_t* dst = isq ? qo + (long)b * ldq + (long)h * D + v * 8 : kc + (long)b * k_bs + (long)p * k_ts + (long)(h - Hq) * D + v * 8;
       *(bf16x8*)dst = oa;
       *(bf16x8*)(dst + half) = ob;
@@ -706,6 +591,70 @@ __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long l
 static constexpr int DA_CHMAX = 512;       // keys one split block handles at most (scores stay in LDS)
 static constexpr float DA_LOG2E = 1.4426950408889634f;
 
+// The two split kernels (bf16 and e4m3 caches) differ in their score and P V loops only; the three phases around them are shared.
+// Keys [s0, s0 + cnt) of block (split blockIdx.x of gridDim.x, blockIdx.y = hkv, blockIdx.z = b), and where its partial goes: an even
+// share of the window's / sequence's keys per split.  cnt <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
+template <int D, int G>
+__device__ __forceinline__ float* da_split_range(const int* kv_len, int Smax, int window, float* ws, int Hkv, int& s0, int& cnt) {
+  const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  const int len = min(kv_len[b], Smax);
+  const int lo = window > 0 ? max(0, len - window) : 0;
+  const int nk = max(0, len - lo);
+  const int ch = (nk + ns - 1) / ns;
+  s0 = lo + min(nk, s * ch);
+  cnt = lo + min(nk, (s + 1) * ch) - s0;
+  return ws + (((long)b * Hkv + hkv) * ns + s) * G * (D + 2);
+}
+
+// scores sc[g][0 .. cnt) (log2 domain) -> p_j = 2^(score - max) in place, ml[g] = (max, sum); wave w handles heads w, w + 4, ...  A barrier
+// on either side: the scores come from, and the p_j go to, other threads
+template <int G>
+__device__ __forceinline__ void da_softmax(float (*sc)[DA_CHMAX], float (*ml)[2], int cnt, int w, int lane) {
+  __syncthreads();
+  for (int g = w; g < G; g += 4) {
+    float mx = -INFINITY;
+    for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, sc[g][j]);
+    mx = wave_max(mx);
+    float l = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+      const float pj = exp2f(sc[g][j] - mx);
+      sc[g][j] = pj;
+      l += pj;
+    }
+    l = wave_sum(l);
+    if (lane == 0) { ml[g][0] = mx; ml[g][1] = l; }
+  }
+  __syncthreads();
+}
+
+// acc[g][x]: a lane's P V sums for elements e + x (EPL per lane, LPK lanes per key row).  Key groups of a wave (lanes sl, sl + LPK, ...)
+// -> one, then the 4 waves in a fixed order -> the partial: D unnormalised outputs per head, then m, l
+template <int D, int G, int EPL, int LPK>
+__device__ __forceinline__ void da_reduce_store(float (&acc)[G][EPL], float (*red)[G][D], const float (*ml)[2], float* out, int cnt, int e,
+                                                bool act, int w, int lane) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int x = 0; x < EPL; ++x)
+#pragma unroll
+      for (int o = LPK; o < 64; o <<= 1) acc[g][x] += __shfl_xor(acc[g][x], o, 64);
+  if (lane < LPK && act)
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int x = 0; x < EPL; ++x) red[w][g][e + x] = acc[g][x];
+  __syncthreads();
+  for (int i = tid; i < G * D; i += 256) {
+    const int g = i / D, dd = i % D;
+    out[g * (D + 2) + dd] = ((red[0][g][dd] + red[1][g][dd]) + red[2][g][dd]) + red[3][g][dd];
+  }
+  if (tid < G) {
+    out[tid * (D + 2) + D] = cnt > 0 ? ml[tid][0] : -INFINITY;
+    out[tid * (D + 2) + D + 1] = cnt > 0 ? ml[tid][1] : 0.f;
+  }
+}
+
 // grid (nsplit, Hkv, B), 256 threads.  Partial per (b, hkv, split, g): D unnormalised fp32 outputs, then m (log2 domain), l.
 template <int D, int G>
 __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __restrict__ q, long q_bs, const bf16_t* __restrict__ k,
@@ -717,17 +666,12 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __
   __shared__ float sc[G][DA_CHMAX];
   __shared__ float red[4][G][D];
   __shared__ float ml[G][2];
-  const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  const int hkv = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int sl = tid % LPK, ko = tid / LPK, e = sl * 8;
   const bool act = e < D;
-  const int len = min(kv_len[b], Smax);
-  const int lo = window > 0 ? max(0, len - window) : 0;
-  const int nk = max(0, len - lo);
-  const int ch = (nk + ns - 1) / ns;
-  const int s0 = lo + min(nk, s * ch), s1 = lo + min(nk, (s + 1) * ch);
-  const int cnt = s1 - s0;                                       // <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
-  float* out = ws + (((long)b * Hkv + hkv) * ns + s) * G * (D + 2);
+  int s0, cnt;
+  float* out = da_split_range<D, G>(kv_len, Smax, window, ws, Hkv, s0, cnt);
   float qf[G][8];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -757,22 +701,7 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __
 #pragma unroll
       for (int g = 0; g < G; ++g) sc[g][j] = d[g];
   }
-  __syncthreads();
-  // per head: max, exp2, sum (wave w handles heads w, w + 4, ...)
-  for (int g = w; g < G; g += 4) {
-    float mx = -INFINITY;
-    for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, sc[g][j]);
-    mx = wave_max(mx);
-    float l = 0.f;
-    for (int j = lane; j < cnt; j += 64) {
-      const float pj = exp2f(sc[g][j] - mx);
-      sc[g][j] = pj;
-      l += pj;
-    }
-    l = wave_sum(l);
-    if (lane == 0) { ml[g][0] = mx; ml[g][1] = l; }
-  }
-  __syncthreads();
+  da_softmax<G>(sc, ml, cnt, w, lane);
   // P V
   float acc[G][8];
 #pragma unroll
@@ -791,27 +720,7 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __
       }
     }
   }
-  // key groups of a wave (lanes sl, sl + LPK, ...) -> one, then the 4 waves in order
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-#pragma unroll
-      for (int o = LPK; o < 64; o <<= 1) acc[g][x] += __shfl_xor(acc[g][x], o, 64);
-  if (lane < LPK && act)
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int x = 0; x < 8; ++x) red[w][g][e + x] = acc[g][x];
-  __syncthreads();
-  for (int i = tid; i < G * D; i += 256) {
-    const int g = i / D, dd = i % D;
-    out[g * (D + 2) + dd] = ((red[0][g][dd] + red[1][g][dd]) + red[2][g][dd]) + red[3][g][dd];
-  }
-  if (tid < G) {
-    out[tid * (D + 2) + D] = cnt > 0 ? ml[tid][0] : -INFINITY;
-    out[tid * (D + 2) + D + 1] = cnt > 0 ? ml[tid][1] : 0.f;
-  }
+  da_reduce_store<D, G, 8, LPK>(acc, red, ml, out, cnt, e, act, w, lane);
 }
 
 // grid (Hq, B), D threads: o[b, h, :] = sum_s 2^(m_s - M) o_s / sum_s 2^(m_s - M) l_s, splits in order
@@ -844,37 +753,20 @@ __global__ void add_i32_kernel(int* __restrict__ x, long n, int delta) {
 // The third member of the e4m3 / MXFP4 family: the cache itself in OCP e4m3fn bytes with one power-of-two fp32 scale per (token, KV head) —
 // the row contract of fp8_e4m3.h with row length D (quant.py: quantize_kv_heads).  K is quantised after RoPE, V as projected.
 //  - quant_kv_e4m3_kernel: the prefill sink.  One (token, head) row per lane group: absmax -> scale -> bytes (and / or the dequantised
-//    values as bf16 rows of a bf16 cache: the emulated mode, which the bf16 decode attention then reads).
-//  - decode_rope_append_kv8_kernel: decode_rope_append_kernel (the same rounding points: q is bit-identical) with one lane group per head, so
+//    values as bf16 rows of a bf16 cache: the emulated mode, which the bf16 decode attention then reads), with the weight quantiser's
+//    e4m3_absmax8 / e4m3_quant8.
+//  - decode_rope_append_kv8_kernel: decode_rope_append_kernel's rotation (rope_rot8: q is bit-identical) with one lane group per head, so
 //    that the D rotated elements of a k head (the D elements of a v head) meet for their absmax; row pos[b] receives bytes + scale.
-//  - decode_attn_split_kv8_kernel: decode_attn_split_kernel with byte operands: a 16-byte load carries 16 elements, a key row takes half the
-//    lanes and a block pass covers twice the keys.  The bytes are converted exactly in registers (v_cvt_scalef32_pk_bf16_fp8, scale 1); the k
-//    scale multiplies the finished dot product, the v scale multiplies p_j before the P V accumulation (both exact power-of-two products in
-//    fp32).  Partials in decode_attn_split_kernel's layout: decode_attn_combine_kernel and the workspace are shared.
+//  - decode_attn_split_kv8_kernel: the split, softmax and reduction phases of decode_attn_split_kernel (da_split_range, da_softmax,
+//    da_reduce_store) around score and P V loops on byte operands: a 16-byte load carries 16 elements, a key row takes half the lanes and a
+//    block pass covers twice the keys.  The bytes are converted exactly in registers (v_cvt_scalef32_pk_bf16_fp8, scale 1); the k scale
+//    multiplies the finished dot product, the v scale multiplies p_j before the P V accumulation (both exact power-of-two products in
+//    fp32).  The partials have one layout: decode_attn_combine_kernel and the workspace are shared.
 struct KvDst {                               // one of k / v: bytes + scales (q, s: both or neither) and / or dequantised bf16 rows (d)
   uint8_t* q; long q_bs, q_ts;               // strides in bytes
   float* s; long s_bs, s_ts;                 // [B, Smax, Hkv] fp32, strides in elements
   bf16_t* d; long d_bs, d_ts;                // strides in elements
 };
-
-// 8 bf16 of one head -> 8 e4m3fn bytes of v / 2^se and their dequantised values
-__device__ __forceinline__ void kv8_quant8(const bf16x8 v, int se, u32x2& q, bf16x8& d) {
-  uint32_t lo = 0, hi = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint32_t b = vp_e4m3_quant((uint16_t)v[j], se);
-    if (j < 4) lo |= b << (8 * j); else hi |= b << (8 * (j - 4));
-    d[j] = (short)vp_e4m3_dequant_bf16(b, se);
-  }
-  q[0] = lo;
-  q[1] = hi;
-}
-
-__device__ __forceinline__ uint32_t kv8_absmax8(const bf16x8 v, uint32_t am) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) am = max(am, (uint32_t)(uint16_t)v[j] & 0x7fffu);
-  return am;
-}
 
 // n token rows of `heads` heads (2 Hkv for a k|v row); lph lanes per head (a power of two >= D / 8 that divides 64: a head never straddles a
 // wave), lane sl owns elements sl * 8 .. sl * 8 + 7.  Every lane of the block runs every shuffle (the trip count is block-uniform).
@@ -891,13 +783,13 @@ __global__ __launch_bounds__(256) void quant_kv_e4m3_kernel(const bf16_t* __rest
     const long off = (grp % heads) * D + sl * 8;
     bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (act) v = *(const bf16x8*)(src + t * ld_src + off);
-    uint32_t am = kv8_absmax8(v, 0);
+    uint32_t am = e4m3_absmax8(v, 0);
     for (int o = lph >> 1; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
     if (act) {
       const int se = vp_e4m3_scale_exp(am);
       u32x2 qv;
       bf16x8 d;
-      kv8_quant8(v, se, qv, d);
+      e4m3_quant8(v, se, qv, d);
       if (Q) {
         *(u32x2*)(Q + t * ldq + off) = qv;
         if (sl == 0) scale[t * ld_scale + grp % heads] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
@@ -930,20 +822,13 @@ __global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_
       const bf16x8 a = *(const bf16x8*)src, bb = *(const bf16x8*)(src + half);
       if (rot) {
         const int pc = min(max(p, 0), Smax - 1);
-        const float* c = cs + (long)pc * half + sl * 8;
-        const float* s = sn + (long)pc * half + sl * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float x1 = bf2f((bf16_t)a[j]), x2 = bf2f((bf16_t)bb[j]);
-          oa[j] = (short)f2bf(bfround(x1 * c[j]) + bfround(-x2 * s[j]));
-          ob[j] = (short)f2bf(bfround(x2 * c[j]) + bfround(x1 * s[j]));
-        }
+        rope_rot8(a, bb, cs + (long)pc * half + sl * 8, sn + (long)pc * half + sl * 8, oa, ob);
       } else {
         oa = a;
         ob = bb;
       }
     }
-    uint32_t am = kv8_absmax8(ob, kv8_absmax8(oa, 0));
+    uint32_t am = e4m3_absmax8(ob, e4m3_absmax8(oa, 0));
     for (int o = lph >> 1; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
     if (act && h < Hq) {
       bf16_t* dst = qo + (long)b * ldq + (long)h * D + sl * 8;
@@ -954,8 +839,8 @@ __global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_
       const int se = vp_e4m3_scale_exp(am);
       u32x2 qa, qb;
       bf16x8 da, db;
-      kv8_quant8(oa, se, qa, da);
-      kv8_quant8(ob, se, qb, db);
+      e4m3_quant8(oa, se, qa, da);
+      e4m3_quant8(ob, se, qb, db);
       uint8_t* qp = rot ? kd.q : vd.q;
       if (qp) {
         qp += (rot ? (long)b * kd.q_bs + (long)p * kd.q_ts : (long)b * vd.q_bs + (long)p * vd.q_ts) + (long)hk * D + sl * 8;
@@ -1005,17 +890,12 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
   __shared__ float sc[G][DA_CHMAX];
   __shared__ float red[4][G][D];
   __shared__ float ml[G][2];
-  const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  const int hkv = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int sl = tid % LPK, ko = tid / LPK, e = sl * 16;
   const bool act = e < D;
-  const int len = min(kv_len[b], Smax);
-  const int lo = window > 0 ? max(0, len - window) : 0;
-  const int nk = max(0, len - lo);
-  const int ch = (nk + ns - 1) / ns;
-  const int s0 = lo + min(nk, s * ch), s1 = lo + min(nk, (s + 1) * ch);
-  const int cnt = s1 - s0;                                       // <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
-  float* out = ws + (((long)b * Hkv + hkv) * ns + s) * G * (D + 2);
+  int s0, cnt;
+  float* out = da_split_range<D, G>(kv_len, Smax, window, ws, Hkv, s0, cnt);
   const uint8_t* kb = k + (long)b * k_bs + (long)hkv * D + e;
   const uint8_t* vb = v + (long)b * v_bs + (long)hkv * D + e;
   const float* ksb = ksc + (long)b * ks_bs + hkv;
@@ -1064,22 +944,7 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
       }
     }
   }
-  __syncthreads();
-  // per head: max, exp2, sum (wave w handles heads w, w + 4, ...)
-  for (int g = w; g < G; g += 4) {
-    float mx = -INFINITY;
-    for (int j = lane; j < cnt; j += 64) mx = fmaxf(mx, sc[g][j]);
-    mx = wave_max(mx);
-    float l = 0.f;
-    for (int j = lane; j < cnt; j += 64) {
-      const float pj = exp2f(sc[g][j] - mx);
-      sc[g][j] = pj;
-      l += pj;
-    }
-    l = wave_sum(l);
-    if (lane == 0) { ml[g][0] = mx; ml[g][1] = l; }
-  }
-  __syncthreads();
+  da_softmax<G>(sc, ml, cnt, w, lane);
   // P V
   float acc[G][16];
 #pragma unroll
@@ -1114,26 +979,100 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
       }
     }
   }
-  // key groups of a wave (lanes sl, sl + LPK, ...) -> one, then the 4 waves in order
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int x = 0; x < 16; ++x)
-#pragma unroll
-      for (int o = LPK; o < 64; o <<= 1) acc[g][x] += __shfl_xor(acc[g][x], o, 64);
-  if (lane < LPK && act)
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int x = 0; x < 16; ++x) red[w][g][e + x] = acc[g][x];
-  __syncthreads();
-  for (int i = tid; i < G * D; i += 256) {
-    const int g = i / D, dd = i % D;
-    out[g * (D + 2) + dd] = ((red[0][g][dd] + red[1][g][dd]) + red[2][g][dd]) + red[3][g][dd];
+  da_reduce_store<D, G, 16, LPK>(acc, red, ml, out, cnt, e, act, w, lane);
+}
+
+// ---------------------------------------------------------------- host side ---------------
+// What differs between the three GEMM entry points: their wording, the format's divisibility rules, its chunk and its kernels
+struct DgFormat {
+  const char* name;                          // the entry point, for the messages
+  const char* operands;                      // the pointers that must not be null, as the message lists them
+  const char* m_hint;                        // closes the M range of the message
+  const char* rule;                          // the shape rule, as the message states it
+  int kchunk;                                // the split rule's chunk
+  int kmul, ldwmul, kper;                    // K, ldw must be multiples of kmul, ldwmul; ldw >= K / kper
+  bool rowscale, blocks;                     // needs w_scale | E and lde >= K / 32
+  void (*kernel[2])(DecGemmArgs);            // without | with the norm prologue
+};
+static const DgFormat DG_BF16 = {"vp_decode_gemm", "A / W / C", "; larger M: vp_gemm_bf16", "K, lda, ldw multiples of 8, lda / ldw >= K",
+                                 DG_KCHUNK, 8, 8, 1, false, false, {decode_gemm_kernel<false>, decode_gemm_kernel<true>}};
+static const DgFormat DG_W8 = {"vp_decode_gemm_w8", "A / W / w_scale / C", "", "K, ldw multiples of 16, lda of 8, lda / ldw >= K",
+                               DG8_KCHUNK, 16, 16, 1, true, false, {decode_gemm_w8_kernel<false>, decode_gemm_w8_kernel<true>}};
+static const DgFormat DG_W4 = {"vp_decode_gemm_w4", "A / W / E (block scales) / C", "",
+                               "K a multiple of 32, ldw (bytes) of 16, lda of 8, lda >= K, ldw >= K / 2, lde >= K / 32",
+                               DG4_KCHUNK, 32, 16, 2, false, true, {decode_gemm_w4_kernel<false>, decode_gemm_w4_kernel<true>}};
+
+static long dg_workspace_bytes(int M, int N, int K, int epilogue, int kchunk) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const int ks = dg_ksplit(N, K, epilogue, kchunk);
+  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
+}
+
+// the three GEMM entry points: checks, the main kernel and, where K is split, the combine
+static int dg_run(const DgFormat& f, int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale,
+                  const void* E, long lde, void* C, long ldc, const void* residual, long ldr, const void* norm_w, float eps, int epilogue,
+                  int out_f32, float* workspace, hipStream_t stream) {
+  VP_REQUIRE(A && W && C && (!f.rowscale || w_scale) && (!f.blocks || E), VP_ERR_BAD_ARG, "%s: null %s", f.name, f.operands);
+  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "%s: M = %d (1 <= M <= 16%s)", f.name, M, f.m_hint);
+  char lde_s[40] = "";
+  if (f.blocks) snprintf(lde_s, sizeof(lde_s), ", lde = %ld", lde);
+  VP_REQUIRE(N > 0 && K > 0 && K % f.kmul == 0 && lda % 8 == 0 && ldw % f.ldwmul == 0 && lda >= K && ldw >= K / f.kper &&
+             (!f.blocks || lde >= K / 32), VP_ERR_UNSUPPORTED_SHAPE, "%s: N = %d, K = %d, lda = %ld, ldw = %ld%s (%s)", f.name, N, K, lda,
+             ldw, lde_s, f.rule);
+  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
+             "%s: A, W and norm_w must be 16-byte aligned", f.name);
+  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
+  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "%s: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)", f.name,
+             epilogue);
+  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
+             "%s: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", f.name, N);
+  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "%s: residual epilogue writes bf16 only", f.name);
+  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "%s: ldc / ldr too small", f.name);
+  const int ks = dg_ksplit(N, K, epilogue, f.kchunk);
+  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "%s: this shape splits K %d ways and needs %s_workspace_bytes() of workspace (got NULL)",
+             f.name, ks, f.name);
+  const DecGemmArgs p{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
+                      M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps, w_scale, (const uint8_t*)E, lde};
+  hipLaunchKernelGGL(f.kernel[norm_w != nullptr], dim3(swiglu ? N / 16 : (N + 15) / 16, ks), dim3(DG_THREADS), 0, stream, p);
+  if (ks > 1) {
+    const long nout = (long)M * (swiglu ? N / 2 : N);
+    hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
   }
-  if (tid < G) {
-    out[tid * (D + 2) + D] = cnt > 0 ? ml[tid][0] : -INFINITY;
-    out[tid * (D + 2) + D + 1] = cnt > 0 ? ml[tid][1] : 0.f;
+  return vp_check_launch(f.name);
+}
+
+// the two attention entry points: everything but the format's own stride / alignment rule
+static int da_check(const char* name, bool pointers, const float* workspace, int B, int Hq, int Hkv, int D, int Smax, int window, int nsplit) {
+  VP_REQUIRE(pointers, VP_ERR_BAD_ARG, "%s: null pointer", name);
+  VP_REQUIRE(workspace, VP_ERR_BAD_ARG, "%s: workspace is NULL (vp_decode_attn_workspace_bytes)", name);
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Smax > 0 && window >= 0, VP_ERR_BAD_ARG,
+             "%s: bad sizes (B %d, Hq %d, Hkv %d, Smax %d)", name, B, Hq, Hkv, Smax);
+  const int G = Hq / Hkv;
+  VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d (32 | 64 | 96 | 128)", name, D);
+  VP_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, VP_ERR_UNSUPPORTED_SHAPE, "%s: Hq / Hkv = %d (1 | 2 | 4 | 8)", name, G);
+  VP_REQUIRE(nsplit >= 1 && nsplit <= 1024 && (long)nsplit * DA_CHMAX >= Smax, VP_ERR_UNSUPPORTED_SHAPE,
+             "%s: nsplit %d must cover Smax %d with at most %d keys per split", name, nsplit, Smax, DA_CHMAX);
+  return VP_OK;
+}
+
+// launch(DA_INT<D>, DA_INT<G>) for the head_dim and group size da_check admitted: the instantiation table of both split kernels
+template <int V> struct DA_INT { static constexpr int value = V; };
+template <int D, class F>
+static void da_dispatch_g(int G, F launch) {
+  switch (G) {
+    case 1: launch(DA_INT<D>{}, DA_INT<1>{}); break;
+    case 2: launch(DA_INT<D>{}, DA_INT<2>{}); break;
+    case 4: launch(DA_INT<D>{}, DA_INT<4>{}); break;
+    default: launch(DA_INT<D>{}, DA_INT<8>{}); break;
+  }
+}
+template <class F>
+static void da_dispatch(int D, int G, F launch) {
+  switch (D) {
+    case 32: da_dispatch_g<32>(G, launch); break;
+    case 64: da_dispatch_g<64>(G, launch); break;
+    case 96: da_dispatch_g<96>(G, launch); break;
+    default: da_dispatch_g<128>(G, launch); break;
   }
 }
 
@@ -1145,42 +1084,11 @@ int vp_add_i32(long n, int* x, int delta, hipStream_t stream) {
   return vp_check_launch("vp_add_i32");
 }
 
-long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int ks = dg_ksplit(N, K, epilogue);
-  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
-}
+long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG_KCHUNK); }
 
 int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual,
                    long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, hipStream_t stream) {
-  VP_REQUIRE(A && W && C, VP_ERR_BAD_ARG, "vp_decode_gemm: null A / W / C");
-  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm: M = %d (1 <= M <= 16; larger M: vp_gemm_bf16)", M);
-  VP_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm: N = %d, K = %d, lda = %ld, ldw = %ld (K, lda, ldw multiples of 8, lda / ldw >= K)", N, K, lda, ldw);
-  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm: A, W and norm_w must be 16-byte aligned");
-  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
-  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
-             epilogue);
-  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
-  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm: residual epilogue writes bf16 only");
-  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm: ldc / ldr too small");
-  const int ks = dg_ksplit(N, K, epilogue);
-  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm: this shape splits K %d ways and needs vp_decode_gemm_workspace_bytes() "
-             "of workspace (got NULL)", ks);
-  DecGemmArgs p{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
-                M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps};
-  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
-  if (norm_w)
-    hipLaunchKernelGGL(decode_gemm_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  else
-    hipLaunchKernelGGL(decode_gemm_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  if (ks > 1) {
-    const long nout = (long)M * (swiglu ? N / 2 : N);
-    hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
-  }
-  return vp_check_launch("vp_decode_gemm");
+  return dg_run(DG_BF16, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_quant_rows_e4m3(int N, int K, void* W, long ldw, void* Q, long ldq, float* scale, int writeback, hipStream_t stream) {
@@ -1194,43 +1102,12 @@ int vp_quant_rows_e4m3(int N, int K, void* W, long ldw, void* Q, long ldq, float
   return vp_check_launch("vp_quant_rows_e4m3");
 }
 
-long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int ks = dg8_ksplit(N, K, epilogue);
-  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
-}
+long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG8_KCHUNK); }
 
 int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       hipStream_t stream) {
-  VP_REQUIRE(A && W && C && w_scale, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: null A / W / w_scale / C");
-  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w8: M = %d (1 <= M <= 16)", M);
-  VP_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && lda % 8 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm_w8: N = %d, K = %d, lda = %ld, ldw = %ld (K, ldw multiples of 16, lda of 8, lda / ldw >= K)", N, K, lda, ldw);
-  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm_w8: A, W and norm_w must be 16-byte aligned");
-  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
-  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
-             epilogue);
-  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm_w8: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
-  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm_w8: residual epilogue writes bf16 only");
-  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm_w8: ldc / ldr too small");
-  const int ks = dg8_ksplit(N, K, epilogue);
-  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm_w8: this shape splits K %d ways and needs "
-             "vp_decode_gemm_w8_workspace_bytes() of workspace (got NULL)", ks);
-  DecGemmW8Args p{{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
-                   M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps}, w_scale};
-  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
-  if (norm_w)
-    hipLaunchKernelGGL(decode_gemm_w8_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  else
-    hipLaunchKernelGGL(decode_gemm_w8_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  if (ks > 1) {
-    const long nout = (long)M * (swiglu ? N / 2 : N);
-    hipLaunchKernelGGL(decode_gemm_w8_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
-  }
-  return vp_check_launch("vp_decode_gemm_w8");
+  return dg_run(DG_W8, M, N, K, A, lda, W, ldw, w_scale, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_quant_blocks_mxfp4(int N, int K, void* W, long ldw, void* Q, long ldq, void* E, long lde, int writeback, hipStream_t stream) {
@@ -1245,44 +1122,12 @@ int vp_quant_blocks_mxfp4(int N, int K, void* W, long ldw, void* Q, long ldq, vo
   return vp_check_launch("vp_quant_blocks_mxfp4");
 }
 
-long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int ks = dg4_ksplit(N, K, epilogue);
-  return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
-}
+long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG4_KCHUNK); }
 
 int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       hipStream_t stream) {
-  VP_REQUIRE(A && W && C && E, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: null A / W / E (block scales) / C");
-  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w4: M = %d (1 <= M <= 16)", M);
-  VP_REQUIRE(N > 0 && K > 0 && K % 32 == 0 && lda % 8 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K / 2 && lde >= K / 32,
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_gemm_w4: N = %d, K = %d, lda = %ld, ldw = %ld, lde = %ld (K a multiple of 32, ldw (bytes) of 16, "
-             "lda of 8, lda >= K, ldw >= K / 2, lde >= K / 32)", N, K, lda, ldw, lde);
-  VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm_w4: A, W and norm_w must be 16-byte aligned");
-  const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
-  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)",
-             epilogue);
-  VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_gemm_w4: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", N);
-  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "vp_decode_gemm_w4: residual epilogue writes bf16 only");
-  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "vp_decode_gemm_w4: ldc / ldr too small");
-  const int ks = dg4_ksplit(N, K, epilogue);
-  VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "vp_decode_gemm_w4: this shape splits K %d ways and needs "
-             "vp_decode_gemm_w4_workspace_bytes() of workspace (got NULL)", ks);
-  DecGemmW4Args p{{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
-                   M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps}, (const uint8_t*)E, lde};
-  const int tiles = swiglu ? N / 16 : (N + 15) / 16;
-  if (norm_w)
-    hipLaunchKernelGGL(decode_gemm_w4_kernel<true>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  else
-    hipLaunchKernelGGL(decode_gemm_w4_kernel<false>, dim3(tiles, ks), dim3(DG_THREADS), 0, stream, p);
-  if (ks > 1) {
-    const long nout = (long)M * (swiglu ? N / 2 : N);
-    hipLaunchKernelGGL(decode_gemm_w4_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p.g);
-  }
-  return vp_check_launch("vp_decode_gemm_w4");
+  return dg_run(DG_W4, M, N, K, A, lda, W, ldw, nullptr, E, lde, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
@@ -1307,38 +1152,15 @@ long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit) {
 int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts, const void* v,
                    long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                    hipStream_t stream) {
-  VP_REQUIRE(q && k && v && o && kv_len, VP_ERR_BAD_ARG, "vp_decode_attn: null pointer");
-  VP_REQUIRE(workspace, VP_ERR_BAD_ARG, "vp_decode_attn: workspace is NULL (vp_decode_attn_workspace_bytes)");
-  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Smax > 0 && window >= 0, VP_ERR_BAD_ARG,
-             "vp_decode_attn: bad sizes (B %d, Hq %d, Hkv %d, Smax %d)", B, Hq, Hkv, Smax);
-  const int G = Hq / Hkv;
-  VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: head_dim %d (32 | 64 | 96 | 128)", D);
-  VP_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: Hq / Hkv = %d (1 | 2 | 4 | 8)", G);
-  VP_REQUIRE(nsplit >= 1 && nsplit <= 1024 && (long)nsplit * DA_CHMAX >= Smax, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_attn: nsplit %d must cover Smax %d with at most %d keys per split", nsplit, Smax, DA_CHMAX);
+  if (const int rc = da_check("vp_decode_attn", q && k && v && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window, nsplit)) return rc;
   VP_REQUIRE(q_bs % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
              ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
              VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: strides must be multiples of 8 elements, bases 16-byte aligned");
-  const dim3 grid(nsplit, Hkv, B);
-#define DA_LAUNCH(DD, GG)                                                                                                             \
-  hipLaunchKernelGGL((decode_attn_split_kernel<DD, GG>), grid, dim3(256), 0, stream, (const bf16_t*)q, q_bs, (const bf16_t*)k, k_bs, \
-                     k_ts, (const bf16_t*)v, v_bs, v_ts, kv_len, Smax, window, scale, workspace, Hkv)
-#define DA_G(DD)                          \
-  switch (G) {                            \
-    case 1: DA_LAUNCH(DD, 1); break;      \
-    case 2: DA_LAUNCH(DD, 2); break;      \
-    case 4: DA_LAUNCH(DD, 4); break;      \
-    default: DA_LAUNCH(DD, 8); break;     \
-  }
-  switch (D) {
-    case 32: DA_G(32); break;
-    case 64: DA_G(64); break;
-    case 96: DA_G(96); break;
-    default: DA_G(128); break;
-  }
-#undef DA_G
-#undef DA_LAUNCH
-  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, G, D, nsplit);
+  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
+    hipLaunchKernelGGL((decode_attn_split_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
+                       (const bf16_t*)k, k_bs, k_ts, (const bf16_t*)v, v_bs, v_ts, kv_len, Smax, window, scale, workspace, Hkv);
+  });
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
   return vp_check_launch("vp_decode_attn");
 }
 
@@ -1394,39 +1216,18 @@ int vp_decode_attn_kv8(int B, int Hq, int Hkv, int D, int Smax, const void* q, l
                        const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale, long vs_bs,
                        long vs_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                        hipStream_t stream) {
-  VP_REQUIRE(q && k && v && k_scale && v_scale && o && kv_len, VP_ERR_BAD_ARG, "vp_decode_attn_kv8: null pointer");
-  VP_REQUIRE(workspace, VP_ERR_BAD_ARG, "vp_decode_attn_kv8: workspace is NULL (vp_decode_attn_workspace_bytes)");
-  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Smax > 0 && window >= 0, VP_ERR_BAD_ARG,
-             "vp_decode_attn_kv8: bad sizes (B %d, Hq %d, Hkv %d, Smax %d)", B, Hq, Hkv, Smax);
-  const int G = Hq / Hkv;
-  VP_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: head_dim %d (32 | 64 | 96 | 128)", D);
-  VP_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: Hq / Hkv = %d (1 | 2 | 4 | 8)", G);
-  VP_REQUIRE(nsplit >= 1 && nsplit <= 1024 && (long)nsplit * DA_CHMAX >= Smax, VP_ERR_UNSUPPORTED_SHAPE,
-             "vp_decode_attn_kv8: nsplit %d must cover Smax %d with at most %d keys per split", nsplit, Smax, DA_CHMAX);
+  if (const int rc = da_check("vp_decode_attn_kv8", q && k && v && k_scale && v_scale && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window,
+                              nsplit))
+    return rc;
   VP_REQUIRE(q_bs % 8 == 0 && k_bs % 16 == 0 && k_ts % 16 == 0 && v_bs % 16 == 0 && v_ts % 16 == 0 &&
              ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
              VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: q stride must be a multiple of 8 elements, k / v strides of 16 bytes, bases 16-byte aligned");
-  const dim3 grid(nsplit, Hkv, B);
-#define DA8_LAUNCH(DD, GG)                                                                                                             \
-  hipLaunchKernelGGL((decode_attn_split_kv8_kernel<DD, GG>), grid, dim3(256), 0, stream, (const bf16_t*)q, q_bs, (const uint8_t*)k,   \
-                     k_bs, k_ts, k_scale, ks_bs, ks_ts, (const uint8_t*)v, v_bs, v_ts, v_scale, vs_bs, vs_ts, kv_len, Smax, window,   \
-                     scale, workspace, Hkv)
-#define DA8_G(DD)                          \
-  switch (G) {                             \
-    case 1: DA8_LAUNCH(DD, 1); break;      \
-    case 2: DA8_LAUNCH(DD, 2); break;      \
-    case 4: DA8_LAUNCH(DD, 4); break;      \
-    default: DA8_LAUNCH(DD, 8); break;     \
-  }
-  switch (D) {
-    case 32: DA8_G(32); break;
-    case 64: DA8_G(64); break;
-    case 96: DA8_G(96); break;
-    default: DA8_G(128); break;
-  }
-#undef DA8_G
-#undef DA8_LAUNCH
-  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, G, D, nsplit);
+  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
+    hipLaunchKernelGGL((decode_attn_split_kv8_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
+                       (const uint8_t*)k, k_bs, k_ts, k_scale, ks_bs, ks_ts, (const uint8_t*)v, v_bs, v_ts, v_scale, vs_bs, vs_ts, kv_len,
+                       Smax, window, scale, workspace, Hkv);
+  });
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
   return vp_check_launch("vp_decode_attn_kv8");
 }
 

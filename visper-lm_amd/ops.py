@@ -692,16 +692,14 @@ def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f3
     if ws is None:
         nb = decode_gemm_ws_bytes(M, N, K, epi, w8, w4)
         ws = torch.empty(max(1, nb // 4), device=a.device, dtype=torch.float32) if nb > 0 else None
+    head = (M, N, K, _p(a), lda, _p(w), ldw)
+    tail = (_p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps), int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
     if w8:
-        _lib.call("vp_decode_gemm_w8", M, N, K, _p(a), lda, _p(w), ldw, _p(w_scale), _p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps),
-                  int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
-        return out
-    if w4:
-        _lib.call("vp_decode_gemm_w4", M, N, K, _p(a), lda, _p(w), ldw, _p(w_block_scale), w_block_scale.stride(0), _p(out), ldc, _p(residual),
-                  ldr, _p(norm_w), float(eps), int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
-        return out
-    _lib.call("vp_decode_gemm", M, N, K, _p(a), lda, _p(w), ldw, _p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps), int(epi),
-              1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
+        _lib.call("vp_decode_gemm_w8", *head, _p(w_scale), *tail)
+    elif w4:
+        _lib.call("vp_decode_gemm_w4", *head, _p(w_block_scale), w_block_scale.stride(0), *tail)
+    else:
+        _lib.call("vp_decode_gemm", *head, *tail)
     return out
 
 
@@ -747,9 +745,9 @@ def decode_attn_splits(B, Hkv, Smax, cus=256):
     return min(1024, max(ns, -(-Smax // 512)))
 
 
-def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
-    """q [B, Hq*D] rows, caches [B, Smax, Hkv, D], kv_len int32 [B] (device) -> o [B, Hq*D] bf16."""
-    B, Smax, Hkv, D = k_cache.shape
+def _decode_attn_defaults(q, cache, Hq, scale, nsplit, out, ws):
+    """(scale, nsplit, out, ws) of decode_attn / decode_attn_kv8 with the caller's None filled in; cache [B, Smax, Hkv, D]."""
+    B, Smax, Hkv, D = cache.shape
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if nsplit is None:
@@ -758,6 +756,13 @@ def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=No
         out = torch.empty(B, Hq * D, device=q.device, dtype=BF16)
     if ws is None:
         ws = torch.empty(_lib.raw("vp_decode_attn_workspace_bytes", B, Hq, Hkv, D, nsplit) // 4, device=q.device, dtype=torch.float32)
+    return scale, nsplit, out, ws
+
+
+def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+    """q [B, Hq*D] rows, caches [B, Smax, Hkv, D], kv_len int32 [B] (device) -> o [B, Hq*D] bf16."""
+    B, Smax, Hkv, D = k_cache.shape
+    scale, nsplit, out, ws = _decode_attn_defaults(q, k_cache, Hq, scale, nsplit, out, ws)
     kb, kt = _bshd(k_cache)
     vb, vt = _bshd(v_cache)
     _lib.call("vp_decode_attn", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt, _p(out), out.stride(0),
@@ -824,14 +829,7 @@ def decode_attn_kv8(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, Hq, window=0,
     B, Smax, Hkv, D = k_bytes.shape
     assert k_bytes.dtype == torch.uint8 and v_bytes.dtype == torch.uint8 and tuple(v_bytes.shape) == (B, Smax, Hkv, D)
     assert k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32 and tuple(k_scale.shape) == tuple(v_scale.shape) == (B, Smax, Hkv)
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    if nsplit is None:
-        nsplit = decode_attn_splits(B, Hkv, Smax)
-    if out is None:
-        out = torch.empty(B, Hq * D, device=q.device, dtype=BF16)
-    if ws is None:
-        ws = torch.empty(_lib.raw("vp_decode_attn_workspace_bytes", B, Hq, Hkv, D, nsplit) // 4, device=q.device, dtype=torch.float32)
+    scale, nsplit, out, ws = _decode_attn_defaults(q, k_bytes, Hq, scale, nsplit, out, ws)
     kb, kt = _bshd(k_bytes)
     vb, vt = _bshd(v_bytes)
     ksb, kst = _bsh(k_scale)
