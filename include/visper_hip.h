@@ -305,6 +305,37 @@ int vp_decode_attn_kv8(int B, int Hq, int Hkv, int D, int Smax, const void* q, l
                        const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale, long vs_bs,
                        long vs_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                        vp_stream_t stream);
+/* Row-mapped siblings of the four entry points above, for the verify step of prompt-lookup decoding (HF generate(prompt_lookup_num_tokens=n):
+ * transformers/generation/candidate_generator.py PromptLookupCandidateGenerator + utils.py _assisted_decoding): the n + 1 rows of a sequence
+ * (its last token and n drafts) are batch rows of their own that share the sequence's cache row.  Each is its sibling plus one argument,
+ * cache_row: int32 [B] on the device; batch row r writes to / reads from cache row cache_row[r] (K / V bytes, bf16 rows and scales alike),
+ * while pos[r], kv_len[r], q, q_out, o and the workspace stay indexed by r.  NULL = identity: the sibling itself (same kernels, same launch
+ * sequence, bit-identical results).  Same argument checks and error codes as the siblings.  The caller's contract, not checked on the
+ * device: every cache_row[r] lies in [0, rows of the cache); two rows of one append launch may name the same cache row with different pos,
+ * but no two rows may carry the same (cache_row, pos) pair (they would write the same cache row in an unspecified order).  A row's results
+ * are a function of its own q, kv_len, window, nsplit and the keys it reads, so row r equals the sibling's row on a cache whose row r is a
+ * copy of row cache_row[r], bit for bit. */
+int vp_decode_rope_append_rows(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
+                               long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t, const int* pos,
+                               const int* cache_row, int Smax, vp_stream_t stream);
+int vp_decode_attn_rows(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                        const void* v, long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window,
+                        float scale, int nsplit, float* workspace, vp_stream_t stream);
+int vp_decode_rope_append_kv8_rows(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_bytes,
+                                   long k_bs, long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs, long ks_ts,
+                                   float* v_scale, long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq, long vd_bs,
+                                   long vd_ts, const float* cos_t, const float* sin_t, const int* pos, const int* cache_row, int Smax,
+                                   vp_stream_t stream);
+int vp_decode_attn_kv8_rows(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                            const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale,
+                            long vs_bs, long vs_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window, float scale,
+                            int nsplit, float* workspace, vp_stream_t stream);
+/* The device half of the acceptance rule of that verify step, and the next step's counters.  B sequences of n + 1 rows; all arrays int32
+ * on the device.  next [B (n + 1)]: the argmax of every row's logits (read only).  tok [B (n + 1)]: what the rows were fed (row (b, 0) the
+ * last emitted token, rows (b, 1 .. n) the drafts).  Per sequence: n_acc[b] = the largest j <= n with tok[b, i] == next[b, i - 1] for all
+ * 1 <= i <= j; base_pos[b] += n_acc[b] + 1; pos[b, i] = base_pos[b] + i and kv_len[b, i] = pos[b, i] + 1 for the next step's rows;
+ * tok[b, 0] = next[b, n_acc[b]].  n = 0 is the one-token step's + 1.  No workspace.  Null pointers, B <= 0 or n < 0: VP_ERR_BAD_ARG. */
+int vp_decode_accept(int B, int n, const int* next, int* tok, int* base_pos, int* pos, int* kv_len, int* n_acc, vp_stream_t stream);
 /* x[i] += delta for n int32 on the device (the per-sequence position / length counters of a decode step, advanced without a host round trip) */
 int vp_add_i32(long n, int* x, int delta, vp_stream_t stream);
 

@@ -26,6 +26,16 @@ engine and prompts.  The JSON carries every run and the cache bytes of both legs
 below the fastest bf16-cache run.
 
   python tools/decode_bench.py --model phi3 --weights mxfp4 --kv fp8 --out profiles/decode_bench_phi3_kvfp8.json
+
+--lookup N: prompt-lookup decoding with N drafts per step at the chosen --weights / --kv (fp8: the fp8 cache).  Three legs alternate,
+--repeats runs each, in one process on the same engine and prompts: the plain step (which also records the greedy continuation), the verify
+step with a drafter that is always wrong (acceptance 0: the pure cost of a verify step) and with the recorded continuation (every draft
+accepted).  Each leg reads its tokens on the host once per step, as generate() does.  Reported: ms per plain step, ms per verify step and
+their ratio c; a verify step emits 1 + a tokens, so lookup pays when the mean number of accepted drafts per step a exceeds c - 1.  The
+tool asserts that both lookup legs reproduce the plain leg's tokens.  Batch sizes with B (N + 1) > 16 are skipped.  Default --out:
+profiles/decode_bench_{llama3,phi3}_lookup.json.
+
+  python tools/decode_bench.py --model llama3 --lookup 7 --batches 1
 """
 import argparse
 import json
@@ -163,6 +173,87 @@ def kv_legs(eng, weights, B, new, text_tokens, repeats, use_graph):
                 runs=legs["bf16"] + legs["fp8"])
 
 
+def time_lookup(eng, B, new, text_tokens, use_graph, kv, n, leg, ref):
+    """One leg of --lookup: `new` tokens per sequence after the prefill.  leg "plain": the one-token step (returns the tokens [B, new + n] it
+    chose, the other legs' drafts); "wrong" / "true": verify steps of n drafts that are all wrong / all right."""
+    from visper_lm_amd import decode
+    ids, images = prompt(eng, B, text_tokens)
+    V = eng.fz["embed"].shape[0]
+    plain = leg == "plain"
+    sess = decode.DecodeSession(eng, kv_cache_dtype=kv, lookup=0 if plain else n)
+    sess.use_graph = use_graph
+    total = new + n if plain else new                         # the plain leg runs n tokens on: the last verify step's drafts
+    with torch.no_grad():
+        logits = sess.prefill(ids, None, images, None, total + 1)
+        prompt_rows = int(sess.cache.lens_host.max())
+        tok = torch.argmax(logits, -1)
+        toks = [tok.cpu()]
+        if plain:
+            toks.append(torch.argmax(sess.step(tok), -1).cpu())               # first step: capture (graph) / warm-up (eager), not timed
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            while len(toks) < total:
+                toks.append(torch.argmax(sess.step(toks[-1].cuda()), -1).cpu())          # one host read per step, as generate()'s loop
+            steps, timed = total - 2, total - 2
+            out = torch.stack(toks, 1)
+        else:
+            raw = [[int(t)] for t in toks[0]]
+            drafts = torch.empty(B, n, dtype=torch.int32)
+
+            def one_step():
+                for b in range(B):
+                    c = len(raw[b])
+                    d = ref[b, c:c + n]
+                    drafts[b] = (d if leg == "true" else (d + 1) % V).to(torch.int32)
+                nxt, n_acc = sess.verify(drafts)
+                for b in range(B):
+                    raw[b].extend(nxt[b, :int(n_acc[b]) + 1].tolist())
+
+            sess.feed(tok)
+            one_step()                                                            # capture / warm-up, not timed
+            torch.cuda.synchronize()
+            first = min(len(r) for r in raw)
+            t0 = time.perf_counter()
+            while min(len(r) for r in raw) < new:
+                one_step()
+            steps, timed = sess.steps - 1, min(len(r) for r in raw) - first
+            out = torch.tensor([r[:new] for r in raw])
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+    if not plain:
+        assert torch.equal(out, ref[:, :new]), f"lookup leg {leg}: tokens differ from the plain leg's"
+        assert sess.accepted == (B * n * sess.steps if leg == "true" else 0), (leg, sess.steps, sess.accepted)
+    r = dict(B=B, leg=leg, n=0 if plain else n, graph=use_graph, steps_timed=steps, tokens_timed=timed, ms_per_step=round(ms / steps, 4),
+             ms_per_token=round(ms / timed, 4), prompt_rows=prompt_rows, kv_cache_bytes=int(sess.cache.nbytes))
+    return r, out
+
+
+def lookup_legs(eng, B, new, text_tokens, repeats, use_graph, kv, n):
+    """plain, always-wrong and always-right legs alternately -> dict with every run, the medians, c and the verdict"""
+    legs = {"plain": [], "wrong": [], "true": []}
+    ref = None
+    for _ in range(repeats):
+        for leg in legs:
+            r, out = time_lookup(eng, B, new, text_tokens, use_graph, kv, n, leg, ref)
+            if leg == "plain":
+                assert ref is None or torch.equal(ref, out), "the plain leg is not reproducible"
+                ref = out
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    step = {k: [r["ms_per_step"] for r in v] for k, v in legs.items()}
+    per_tok = {k: [r["ms_per_token"] for r in v] for k, v in legs.items()}
+    c = med(step["wrong"]) / med(step["plain"])
+    gain = max(per_tok["true"]) < min(per_tok["plain"])
+    return dict(B=B, n=n, graph=use_graph, repeats=repeats, plain_ms_per_step=step["plain"], verify_ms_per_step_acceptance_0=step["wrong"],
+                verify_ms_per_step_full_acceptance=step["true"], plain_median=med(step["plain"]), verify_median=med(step["wrong"]),
+                c=round(c, 4), break_even_accepted_drafts_per_step=round(c - 1, 4),
+                full_acceptance_ms_per_token=per_tok["true"], plain_ms_per_token=per_tok["plain"],
+                slowest_full_acceptance_ms_per_token=max(per_tok["true"]), fastest_plain_ms_per_token=min(per_tok["plain"]),
+                verdict_at_full_acceptance="gain" if gain else "no gain",
+                acceptance_0_costs=bool(min(step["wrong"]) > max(step["plain"])), runs=legs["plain"] + legs["wrong"] + legs["true"])
+
+
 def weight_bytes(eng):
     cfg = eng.cfg
     H, I, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
@@ -185,13 +276,29 @@ def main():
     ap.add_argument("--graph", action="store_true", help="--weights fp8 / mxfp4: time the captured step instead of eager launches")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: at the chosen --weights, bf16-cache and fp8-cache legs alternately on one engine, --repeats runs each")
+    ap.add_argument("--lookup", type=int, default=0,
+                    help="N > 0: prompt-lookup decoding with N drafts per step: plain, always-wrong and always-right legs, --repeats runs each")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.lookup and not a.out:
+        a.out = os.path.join(ROOT, "profiles", f"decode_bench_{a.model}_lookup.json")
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
     eng = build(a.model, a.layers)
     dec_b, head_b = weight_bytes(eng)
     res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
                roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
+    if a.lookup:
+        if a.weights != "bf16":
+            eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")
+        res.update(weights=a.weights, kv=a.kv, lookup=a.lookup, lm_head_quantised=a.weights != "bf16", cells=[])
+        for B in [int(x) for x in a.batches.split(",")]:
+            if B * (a.lookup + 1) > 16:
+                print(f"B = {B}: skipped, {B * (a.lookup + 1)} verify rows > 16", flush=True)
+                continue
+            cell = lookup_legs(eng, B, a.new, a.text, a.repeats, a.graph, "fp8_e4m3" if a.kv == "fp8" else None, a.lookup)
+            res["runs"] += cell.pop("runs")
+            res["cells"].append(cell)
+        a.weights = a.kv = "lookup"                               # the other modes below do not run
     if a.kv == "fp8":
         if a.weights != "bf16":
             eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")

@@ -85,6 +85,12 @@ _SIGS = {
     "vp_decode_rope_append_kv8": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, p, p, i, p],
     "vp_decode_attn_kv8": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, p, i, f, i, p, p],
     "vp_add_i32": [l, p, i, p],
+    # prompt-lookup decoding: the append / attention entry points with a row map (cache_row after pos / kv_len), and the acceptance rule
+    "vp_decode_rope_append_rows": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, p, p, p, i, p],
+    "vp_decode_attn_rows": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, p, p, i, f, i, p, p],
+    "vp_decode_rope_append_kv8_rows": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, p, p, p, i, p],
+    "vp_decode_attn_kv8_rows": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, p, p, i, f, i, p, p],
+    "vp_decode_accept": [i, i, p, p, p, p, p, p, p],
     "vp_ce_fwd_bwd": [l, i, p, l, p, p, f, i, p],
     "vp_emb_loss_workspace": [i, i, l],
     "vp_sumsq_nblk": [l],

@@ -10,6 +10,9 @@
 //    the host side (dg_run) are one piece of code for the three.
 //  - decode_rope_append_kernel / decode_rope_append_kv8_kernel: rotate-half RoPE of q / k at per-sequence positions pos[b] (vp_rope's
 //    rounding points), k / v appended to row pos[b] of the bf16 | e4m3 cache.
+//  - the *_rows entry points of the append and attention kernels: the same kernels with a row map (cache_row[r] = the cache row that batch
+//    row r writes and reads; the plain entry points pass none), so that the n + 1 rows of a prompt-lookup verify step each run the
+//    one-token computation on their sequence's cache.  decode_accept_kernel: the acceptance rule and the next step's counters.
 //  - decode_attn_split_kernel / decode_attn_split_kv8_kernel + decode_attn_combine_kernel: one query row per sequence, the Hq/Hkv heads of
 //    a KV head share every K / V read, the key range split over `nsplit` blocks (fp32 softmax, log2 domain), combined in a fixed order.
 //  - the quantisers that make the byte operands: quant_rows_e4m3_kernel, quant_blocks_mxfp4_kernel, quant_kv_e4m3_kernel.
@@ -555,17 +558,19 @@ __device__ __forceinline__ void rope_rot8(const bf16x8 a, const bf16x8 b, const 
   }
 }
 
-// qkv [B, ldq] rows (q heads | k heads | v heads); thread = one 8-wide vector of one head's first half (q / k) or 16 elements of v
+// qkv [B, ldq] rows (q heads | k heads | v heads); thread = one 8-wide vector of one head's first half (q / k) or 16 elements of v.
+// cache_row (null: identity): row b appends to cache row cache_row[b]; q_out stays indexed by b
 __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo, long ldq,
                                           bf16_t* __restrict__ kc, long k_bs, long k_ts, bf16_t* __restrict__ vc, long v_bs, long v_ts,
                                           const float* __restrict__ cs, const float* __restrict__ sn, const int* __restrict__ pos,
-                                          int B, int Hq, int Hkv, int D, int Smax) {
+                                          const int* __restrict__ cache_row, int B, int Hq, int Hkv, int D, int Smax) {
   const int half = D >> 1, vph = half >> 3;
   const int per_b = (Hq + Hkv) * vph + Hkv * (D >> 3);
   const long total = (long)B * per_b;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int b = (int)(i / per_b), r = (int)(i % per_b);
     const int p = pos[b];
+    const int cb = cache_row ? cache_row[b] : b;
     const bf16_t* row = qkv + (long)b * ldqkv;
     if (r < (Hq + Hkv) * vph) {
       const int h = r / vph, v = r % vph;
@@ -576,13 +581,13 @@ __global__ void decode_rope_append_kernel(const bf16_t* __restrict__ qkv, long l
       const int pc = min(max(p, 0), Smax - 1);
       bf16x8 oa, ob;
       rope_rot8(a, bb, cs + (long)pc * half + v * 8, sn + (long)pc * half + v * 8, oa, ob);
-      bf16_t* dst = isq ? qo + (long)b * ldq + (long)h * D + v * 8 : kc + (long)b * k_bs + (long)p * k_ts + (long)(h - Hq) * D + v * 8;
+      bf16_t* dst = isq ? qo + (long)b * ldq + (long)h * D + v * 8 : kc + (long)cb * k_bs + (long)p * k_ts + (long)(h - Hq) * D + v * 8;
       *(bf16x8*)dst = oa;
       *(bf16x8*)(dst + half) = ob;
     } else {
       if (p < 0 || p >= Smax) continue;
       const int e = (r - (Hq + Hkv) * vph) * 8;                  // element within the Hkv * D v block
-      *(bf16x8*)(vc + (long)b * v_bs + (long)p * v_ts + e) = *(const bf16x8*)(row + (long)(Hq + Hkv) * D + e);
+      *(bf16x8*)(vc + (long)cb * v_bs + (long)p * v_ts + e) = *(const bf16x8*)(row + (long)(Hq + Hkv) * D + e);
     }
   }
 }
@@ -593,10 +598,13 @@ static constexpr float DA_LOG2E = 1.4426950408889634f;
 
 // The two split kernels (bf16 and e4m3 caches) differ in their score and P V loops only; the three phases around them are shared.
 // Keys [s0, s0 + cnt) of block (split blockIdx.x of gridDim.x, blockIdx.y = hkv, blockIdx.z = b), and where its partial goes: an even
-// share of the window's / sequence's keys per split.  cnt <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX
+// share of the window's / sequence's keys per split.  cnt <= DA_CHMAX: the launcher checks Smax <= nsplit * DA_CHMAX.  cb: the cache row
+// the block reads (cache_row[b]; b itself without a row map); q, kv_len and the partials stay indexed by b
 template <int D, int G>
-__device__ __forceinline__ float* da_split_range(const int* kv_len, int Smax, int window, float* ws, int Hkv, int& s0, int& cnt) {
+__device__ __forceinline__ float* da_split_range(const int* kv_len, const int* cache_row, int Smax, int window, float* ws, int Hkv, int& s0,
+                                                 int& cnt, int& cb) {
   const int s = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z, ns = gridDim.x;
+  cb = cache_row ? cache_row[b] : b;
   const int len = min(kv_len[b], Smax);
   const int lo = window > 0 ? max(0, len - window) : 0;
   const int nk = max(0, len - lo);
@@ -659,8 +667,8 @@ __device__ __forceinline__ void da_reduce_store(float (&acc)[G][EPL], float (*re
 template <int D, int G>
 __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __restrict__ q, long q_bs, const bf16_t* __restrict__ k,
                                                                 long k_bs, long k_ts, const bf16_t* __restrict__ v, long v_bs, long v_ts,
-                                                                const int* __restrict__ kv_len, int Smax, int window, float scale,
-                                                                float* __restrict__ ws, int Hkv) {
+                                                                const int* __restrict__ kv_len, const int* __restrict__ cache_row,
+                                                                int Smax, int window, float scale, float* __restrict__ ws, int Hkv) {
   constexpr int LPK = D <= 32 ? 4 : (D <= 64 ? 8 : 16);         // lanes per key row (16-byte vectors; D = 96 leaves 4 of 16 idle)
   constexpr int KPB = 256 / LPK;                                 // key rows per block pass
   __shared__ float sc[G][DA_CHMAX];
@@ -670,8 +678,8 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int sl = tid % LPK, ko = tid / LPK, e = sl * 8;
   const bool act = e < D;
-  int s0, cnt;
-  float* out = da_split_range<D, G>(kv_len, Smax, window, ws, Hkv, s0, cnt);
+  int s0, cnt, cb;
+  float* out = da_split_range<D, G>(kv_len, cache_row, Smax, window, ws, Hkv, s0, cnt, cb);
   float qf[G][8];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -680,8 +688,8 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(const bf16_t* __
 #pragma unroll
     for (int j = 0; j < 8; ++j) qf[g][j] = bf2f((bf16_t)qv[j]) * (scale * DA_LOG2E);
   }
-  const bf16_t* kb = k + (long)b * k_bs + (long)hkv * D + e;
-  const bf16_t* vb = v + (long)b * v_bs + (long)hkv * D + e;
+  const bf16_t* kb = k + (long)cb * k_bs + (long)hkv * D + e;
+  const bf16_t* vb = v + (long)cb * v_bs + (long)hkv * D + e;
   // scores (log2 domain) -> LDS
   for (int j0 = 0; j0 < cnt; j0 += KPB) {
     const int j = j0 + ko;
@@ -749,6 +757,28 @@ __global__ void add_i32_kernel(int* __restrict__ x, long n, int delta) {
   if (i < n) x[i] += delta;
 }
 
+// ---------------------------------------------------------------- prompt-lookup acceptance ---------------
+// One thread per sequence of a verify step of n + 1 rows: row (b, i) was fed tok[b, i] (row 0: the last emitted token, rows 1 .. n: the
+// drafts) and chose next[b, i].  Draft i stands if every draft before it stands and it is the token row i - 1 chose; n_acc[b] of them do.
+// The sequence moves n_acc[b] + 1 positions; the next step's rows sit at base_pos[b] + i and attend to their own key as the one-token step
+// does (kv_len = pos + 1); its row 0 is fed the token chosen after the last accepted draft.  n = 0: the one-token step's + 1.
+__global__ void decode_accept_kernel(const int* __restrict__ next, int* __restrict__ tok, int* __restrict__ base_pos, int* __restrict__ pos,
+                                     int* __restrict__ kv_len, int* __restrict__ n_acc, int B, int n) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const long r0 = (long)b * (n + 1);
+  int j = 0;
+  while (j < n && tok[r0 + j + 1] == next[r0 + j]) ++j;
+  const int bp = base_pos[b] + j + 1;
+  n_acc[b] = j;
+  base_pos[b] = bp;
+  for (int i = 0; i <= n; ++i) {
+    pos[r0 + i] = bp + i;
+    kv_len[r0 + i] = bp + i + 1;
+  }
+  tok[r0] = next[r0 + j];
+}
+
 // ---------------------------------------------------------------- FP8 (e4m3) KV cache ---------------
 // The third member of the e4m3 / MXFP4 family: the cache itself in OCP e4m3fn bytes with one power-of-two fp32 scale per (token, KV head) —
 // the row contract of fp8_e4m3.h with row length D (quant.py: quantize_kv_heads).  K is quantised after RoPE, V as projected.
@@ -800,11 +830,12 @@ __global__ __launch_bounds__(256) void quant_kv_e4m3_kernel(const bf16_t* __rest
 }
 
 // qkv [B, ldq] rows (q heads | k heads | v heads); lph lanes per head (a power of two >= D / 16), lane sl owns the 8-wide vector sl of the
-// head's first half and its partner in the second half (the rotation pair for q / k)
+// head's first half and its partner in the second half (the rotation pair for q / k).  cache_row: as decode_rope_append_kernel
 __global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_t* __restrict__ qkv, long ldqkv, bf16_t* __restrict__ qo,
                                                                      long ldq, KvDst kd, KvDst vd, const float* __restrict__ cs,
-                                                                     const float* __restrict__ sn, const int* __restrict__ pos, int B, int Hq,
-                                                                     int Hkv, int D, int Smax, int lph) {
+                                                                     const float* __restrict__ sn, const int* __restrict__ pos,
+                                                                     const int* __restrict__ cache_row, int B, int Hq, int Hkv, int D,
+                                                                     int Smax, int lph) {
   const int half = D >> 1, vph = half >> 3;
   const int per_b = (Hq + 2 * Hkv) * lph;
   const long total = (long)B * per_b;
@@ -816,6 +847,7 @@ __global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_
     const bool act = in && sl < vph;
     const bool rot = h < Hq + Hkv;
     const int p = pos[b];
+    const int cb = cache_row ? cache_row[b] : b;
     bf16x8 oa = {0, 0, 0, 0, 0, 0, 0, 0}, ob = {0, 0, 0, 0, 0, 0, 0, 0};
     if (act) {
       const bf16_t* src = qkv + (long)b * ldqkv + (long)h * D + sl * 8;
@@ -843,17 +875,17 @@ __global__ __launch_bounds__(256) void decode_rope_append_kv8_kernel(const bf16_
       e4m3_quant8(ob, se, qb, db);
       uint8_t* qp = rot ? kd.q : vd.q;
       if (qp) {
-        qp += (rot ? (long)b * kd.q_bs + (long)p * kd.q_ts : (long)b * vd.q_bs + (long)p * vd.q_ts) + (long)hk * D + sl * 8;
+        qp += (rot ? (long)cb * kd.q_bs + (long)p * kd.q_ts : (long)cb * vd.q_bs + (long)p * vd.q_ts) + (long)hk * D + sl * 8;
         *(u32x2*)qp = qa;
         *(u32x2*)(qp + half) = qb;
         if (sl == 0) {
-          float* sp = rot ? kd.s + (long)b * kd.s_bs + (long)p * kd.s_ts : vd.s + (long)b * vd.s_bs + (long)p * vd.s_ts;
+          float* sp = rot ? kd.s + (long)cb * kd.s_bs + (long)p * kd.s_ts : vd.s + (long)cb * vd.s_bs + (long)p * vd.s_ts;
           sp[hk] = __builtin_bit_cast(float, vp_pow2_f32_bits(se));
         }
       }
       bf16_t* dp = rot ? kd.d : vd.d;
       if (dp) {
-        dp += (rot ? (long)b * kd.d_bs + (long)p * kd.d_ts : (long)b * vd.d_bs + (long)p * vd.d_ts) + (long)hk * D + sl * 8;
+        dp += (rot ? (long)cb * kd.d_bs + (long)p * kd.d_ts : (long)cb * vd.d_bs + (long)p * vd.d_ts) + (long)hk * D + sl * 8;
         *(bf16x8*)dp = da;
         *(bf16x8*)(dp + half) = db;
       }
@@ -883,8 +915,8 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
                                                                     long k_bs, long k_ts, const float* __restrict__ ksc, long ks_bs, long ks_ts,
                                                                     const uint8_t* __restrict__ v, long v_bs, long v_ts,
                                                                     const float* __restrict__ vsc, long vs_bs, long vs_ts,
-                                                                    const int* __restrict__ kv_len, int Smax, int window, float scale,
-                                                                    float* __restrict__ ws, int Hkv) {
+                                                                    const int* __restrict__ kv_len, const int* __restrict__ cache_row,
+                                                                    int Smax, int window, float scale, float* __restrict__ ws, int Hkv) {
   constexpr int LPK = D <= 32 ? 2 : (D <= 64 ? 4 : 8);          // lanes per key row (16-byte vectors of 16 elements; D = 96 leaves 2 of 8 idle)
   constexpr int KPB = 256 / LPK;                                 // key rows per block pass
   __shared__ float sc[G][DA_CHMAX];
@@ -894,12 +926,12 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int sl = tid % LPK, ko = tid / LPK, e = sl * 16;
   const bool act = e < D;
-  int s0, cnt;
-  float* out = da_split_range<D, G>(kv_len, Smax, window, ws, Hkv, s0, cnt);
-  const uint8_t* kb = k + (long)b * k_bs + (long)hkv * D + e;
-  const uint8_t* vb = v + (long)b * v_bs + (long)hkv * D + e;
-  const float* ksb = ksc + (long)b * ks_bs + hkv;
-  const float* vsb = vsc + (long)b * vs_bs + hkv;
+  int s0, cnt, cb;
+  float* out = da_split_range<D, G>(kv_len, cache_row, Smax, window, ws, Hkv, s0, cnt, cb);
+  const uint8_t* kb = k + (long)cb * k_bs + (long)hkv * D + e;
+  const uint8_t* vb = v + (long)cb * v_bs + (long)hkv * D + e;
+  const float* ksb = ksc + (long)cb * ks_bs + hkv;
+  const float* vsb = vsc + (long)cb * vs_bs + hkv;
   {
     float qf[G][16];
 #pragma unroll
@@ -1076,6 +1108,82 @@ static void da_dispatch(int D, int G, F launch) {
   }
 }
 
+// the append and attention entry points and their *_rows siblings: checks and launches; cache_row null = the plain entry points
+static int rope_append_run(const char* name, int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq,
+                           void* k_cache, long k_bs, long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t,
+                           const int* pos, const int* cache_row, int Smax, hipStream_t stream) {
+  VP_REQUIRE(qkv && q_out && k_cache && v_cache && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "%s: null pointer", name);
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "%s: bad sizes", name);
+  VP_REQUIRE(D % 16 == 0 && ldqkv % 8 == 0 && ldq % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d must be a multiple of 16, strides multiples of 8", name, D);
+  const long total = (long)B * ((Hq + Hkv) * (D / 16) + Hkv * (D / 8));
+  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
+                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, (bf16_t*)k_cache, k_bs, k_ts, (bf16_t*)v_cache, v_bs, v_ts,
+                     cos_t, sin_t, pos, cache_row, B, Hq, Hkv, D, Smax);
+  return vp_check_launch(name);
+}
+
+static int attn_run(const char* name, int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                    const void* v, long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window,
+                    float scale, int nsplit, float* workspace, hipStream_t stream) {
+  if (const int rc = da_check(name, q && k && v && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window, nsplit)) return rc;
+  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
+             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: strides must be multiples of 8 elements, bases 16-byte aligned", name);
+  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
+    hipLaunchKernelGGL((decode_attn_split_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
+                       (const bf16_t*)k, k_bs, k_ts, (const bf16_t*)v, v_bs, v_ts, kv_len, cache_row, Smax, window, scale, workspace, Hkv);
+  });
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
+  return vp_check_launch(name);
+}
+
+static int rope_append_kv8_run(const char* name, int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq,
+                               void* k_bytes, long k_bs, long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs,
+                               long ks_ts, float* v_scale, long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq,
+                               long vd_bs, long vd_ts, const float* cos_t, const float* sin_t, const int* pos, const int* cache_row,
+                               int Smax, hipStream_t stream) {
+  VP_REQUIRE(qkv && q_out && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "%s: null pointer", name);
+  const bool bytes = k_bytes != nullptr, deq = k_deq != nullptr;
+  VP_REQUIRE(bytes == (v_bytes != nullptr) && bytes == (k_scale != nullptr) && bytes == (v_scale != nullptr) && deq == (v_deq != nullptr),
+             VP_ERR_BAD_ARG, "%s: k / v bytes and scales go together, k / v bf16 destinations go together", name);
+  VP_REQUIRE(bytes || deq, VP_ERR_BAD_ARG, "%s: neither a byte nor a bf16 destination", name);
+  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "%s: bad sizes", name);
+  VP_REQUIRE(D % 16 == 0 && D >= 16 && D <= 128 && ldqkv % 8 == 0 && ldq % 8 == 0 && ((((uintptr_t)qkv) | ((uintptr_t)q_out)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: head_dim %d must be a multiple of 16 (at most 128), strides multiples of 8", name, D);
+  VP_REQUIRE(!bytes || (k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
+                        ((((uintptr_t)k_bytes) | ((uintptr_t)v_bytes)) & 7) == 0),
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: byte strides must be multiples of 8, byte bases 8-byte aligned", name);
+  VP_REQUIRE(!deq || (kd_bs % 8 == 0 && kd_ts % 8 == 0 && vd_bs % 8 == 0 && vd_ts % 8 == 0 &&
+                      ((((uintptr_t)k_deq) | ((uintptr_t)v_deq)) & 15) == 0),
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: bf16 strides must be multiples of 8, bf16 bases 16-byte aligned", name);
+  const int lph = D <= 32 ? 2 : (D <= 64 ? 4 : 8);
+  const long total = (long)B * (Hq + 2 * Hkv) * lph;
+  const KvDst kd{(uint8_t*)k_bytes, k_bs, k_ts, k_scale, ks_bs, ks_ts, (bf16_t*)k_deq, kd_bs, kd_ts};
+  const KvDst vd{(uint8_t*)v_bytes, v_bs, v_ts, v_scale, vs_bs, vs_ts, (bf16_t*)v_deq, vd_bs, vd_ts};
+  hipLaunchKernelGGL(decode_rope_append_kv8_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
+                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, kd, vd, cos_t, sin_t, pos, cache_row, B, Hq, Hkv, D, Smax, lph);
+  return vp_check_launch(name);
+}
+
+static int attn_kv8_run(const char* name, int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs,
+                        long k_ts, const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale,
+                        long vs_bs, long vs_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window, float scale,
+                        int nsplit, float* workspace, hipStream_t stream) {
+  if (const int rc = da_check(name, q && k && v && k_scale && v_scale && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window, nsplit))
+    return rc;
+  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 16 == 0 && k_ts % 16 == 0 && v_bs % 16 == 0 && v_ts % 16 == 0 &&
+             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
+             VP_ERR_UNSUPPORTED_SHAPE, "%s: q stride must be a multiple of 8 elements, k / v strides of 16 bytes, bases 16-byte aligned", name);
+  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
+    hipLaunchKernelGGL((decode_attn_split_kv8_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
+                       (const uint8_t*)k, k_bs, k_ts, k_scale, ks_bs, ks_ts, (const uint8_t*)v, v_bs, v_ts, v_scale, vs_bs, vs_ts, kv_len,
+                       cache_row, Smax, window, scale, workspace, Hkv);
+  });
+  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
+  return vp_check_launch(name);
+}
+
 extern "C" {
 
 int vp_add_i32(long n, int* x, int delta, hipStream_t stream) {
@@ -1133,15 +1241,15 @@ int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* 
 int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
                           long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t, const int* pos, int Smax,
                           hipStream_t stream) {
-  VP_REQUIRE(qkv && q_out && k_cache && v_cache && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "vp_decode_rope_append: null pointer");
-  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "vp_decode_rope_append: bad sizes");
-  VP_REQUIRE(D % 16 == 0 && ldqkv % 8 == 0 && ldq % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0,
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append: head_dim %d must be a multiple of 16, strides multiples of 8", D);
-  const long total = (long)B * ((Hq + Hkv) * (D / 16) + Hkv * (D / 8));
-  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
-                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, (bf16_t*)k_cache, k_bs, k_ts, (bf16_t*)v_cache, v_bs, v_ts,
-                     cos_t, sin_t, pos, B, Hq, Hkv, D, Smax);
-  return vp_check_launch("vp_decode_rope_append");
+  return rope_append_run("vp_decode_rope_append", B, Hq, Hkv, D, qkv, ldqkv, q_out, ldq, k_cache, k_bs, k_ts, v_cache, v_bs, v_ts, cos_t,
+                         sin_t, pos, nullptr, Smax, stream);
+}
+
+int vp_decode_rope_append_rows(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,
+                               long k_ts, void* v_cache, long v_bs, long v_ts, const float* cos_t, const float* sin_t, const int* pos,
+                               const int* cache_row, int Smax, hipStream_t stream) {
+  return rope_append_run("vp_decode_rope_append_rows", B, Hq, Hkv, D, qkv, ldqkv, q_out, ldq, k_cache, k_bs, k_ts, v_cache, v_bs, v_ts,
+                         cos_t, sin_t, pos, cache_row, Smax, stream);
 }
 
 long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit) {
@@ -1152,16 +1260,15 @@ long vp_decode_attn_workspace_bytes(int B, int Hq, int Hkv, int D, int nsplit) {
 int vp_decode_attn(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts, const void* v,
                    long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                    hipStream_t stream) {
-  if (const int rc = da_check("vp_decode_attn", q && k && v && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window, nsplit)) return rc;
-  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
-             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn: strides must be multiples of 8 elements, bases 16-byte aligned");
-  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
-    hipLaunchKernelGGL((decode_attn_split_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
-                       (const bf16_t*)k, k_bs, k_ts, (const bf16_t*)v, v_bs, v_ts, kv_len, Smax, window, scale, workspace, Hkv);
-  });
-  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
-  return vp_check_launch("vp_decode_attn");
+  return attn_run("vp_decode_attn", B, Hq, Hkv, D, Smax, q, q_bs, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, kv_len, nullptr, window, scale,
+                  nsplit, workspace, stream);
+}
+
+int vp_decode_attn_rows(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                        const void* v, long v_bs, long v_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window,
+                        float scale, int nsplit, float* workspace, hipStream_t stream) {
+  return attn_run("vp_decode_attn_rows", B, Hq, Hkv, D, Smax, q, q_bs, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, kv_len, cache_row, window,
+                  scale, nsplit, workspace, stream);
 }
 
 int vp_quant_kv_e4m3(long n, int heads, int D, const void* src, long ld_src, void* Q, long ldq, float* scale, long ld_scale, void* deq,
@@ -1189,46 +1296,43 @@ int vp_decode_rope_append_kv8(int B, int Hq, int Hkv, int D, const void* qkv, lo
                               long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs, long ks_ts, float* v_scale,
                               long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq, long vd_bs, long vd_ts,
                               const float* cos_t, const float* sin_t, const int* pos, int Smax, hipStream_t stream) {
-  VP_REQUIRE(qkv && q_out && cos_t && sin_t && pos, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: null pointer");
-  const bool bytes = k_bytes != nullptr, deq = k_deq != nullptr;
-  VP_REQUIRE(bytes == (v_bytes != nullptr) && bytes == (k_scale != nullptr) && bytes == (v_scale != nullptr) && deq == (v_deq != nullptr),
-             VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: k / v bytes and scales go together, k / v bf16 destinations go together");
-  VP_REQUIRE(bytes || deq, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: neither a byte nor a bf16 destination");
-  VP_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Smax > 0, VP_ERR_BAD_ARG, "vp_decode_rope_append_kv8: bad sizes");
-  VP_REQUIRE(D % 16 == 0 && D >= 16 && D <= 128 && ldqkv % 8 == 0 && ldq % 8 == 0 && ((((uintptr_t)qkv) | ((uintptr_t)q_out)) & 15) == 0,
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: head_dim %d must be a multiple of 16 (at most 128), strides multiples of 8", D);
-  VP_REQUIRE(!bytes || (k_bs % 8 == 0 && k_ts % 8 == 0 && v_bs % 8 == 0 && v_ts % 8 == 0 &&
-                        ((((uintptr_t)k_bytes) | ((uintptr_t)v_bytes)) & 7) == 0),
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: byte strides must be multiples of 8, byte bases 8-byte aligned");
-  VP_REQUIRE(!deq || (kd_bs % 8 == 0 && kd_ts % 8 == 0 && vd_bs % 8 == 0 && vd_ts % 8 == 0 &&
-                      ((((uintptr_t)k_deq) | ((uintptr_t)v_deq)) & 15) == 0),
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_rope_append_kv8: bf16 strides must be multiples of 8, bf16 bases 16-byte aligned");
-  const int lph = D <= 32 ? 2 : (D <= 64 ? 4 : 8);
-  const long total = (long)B * (Hq + 2 * Hkv) * lph;
-  const KvDst kd{(uint8_t*)k_bytes, k_bs, k_ts, k_scale, ks_bs, ks_ts, (bf16_t*)k_deq, kd_bs, kd_ts};
-  const KvDst vd{(uint8_t*)v_bytes, v_bs, v_ts, v_scale, vs_bs, vs_ts, (bf16_t*)v_deq, vd_bs, vd_ts};
-  hipLaunchKernelGGL(decode_rope_append_kv8_kernel, dim3((unsigned)min(2048L, (total + 255) / 256)), dim3(256), 0, stream,
-                     (const bf16_t*)qkv, ldqkv, (bf16_t*)q_out, ldq, kd, vd, cos_t, sin_t, pos, B, Hq, Hkv, D, Smax, lph);
-  return vp_check_launch("vp_decode_rope_append_kv8");
+  return rope_append_kv8_run("vp_decode_rope_append_kv8", B, Hq, Hkv, D, qkv, ldqkv, q_out, ldq, k_bytes, k_bs, k_ts, v_bytes, v_bs, v_ts,
+                             k_scale, ks_bs, ks_ts, v_scale, vs_bs, vs_ts, k_deq, kd_bs, kd_ts, v_deq, vd_bs, vd_ts, cos_t, sin_t, pos,
+                             nullptr, Smax, stream);
+}
+
+int vp_decode_rope_append_kv8_rows(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_bytes,
+                                   long k_bs, long k_ts, void* v_bytes, long v_bs, long v_ts, float* k_scale, long ks_bs, long ks_ts,
+                                   float* v_scale, long vs_bs, long vs_ts, void* k_deq, long kd_bs, long kd_ts, void* v_deq, long vd_bs,
+                                   long vd_ts, const float* cos_t, const float* sin_t, const int* pos, const int* cache_row, int Smax,
+                                   hipStream_t stream) {
+  return rope_append_kv8_run("vp_decode_rope_append_kv8_rows", B, Hq, Hkv, D, qkv, ldqkv, q_out, ldq, k_bytes, k_bs, k_ts, v_bytes, v_bs,
+                             v_ts, k_scale, ks_bs, ks_ts, v_scale, vs_bs, vs_ts, k_deq, kd_bs, kd_ts, v_deq, vd_bs, vd_ts, cos_t, sin_t,
+                             pos, cache_row, Smax, stream);
 }
 
 int vp_decode_attn_kv8(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
                        const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale, long vs_bs,
                        long vs_ts, void* o, long o_bs, const int* kv_len, int window, float scale, int nsplit, float* workspace,
                        hipStream_t stream) {
-  if (const int rc = da_check("vp_decode_attn_kv8", q && k && v && k_scale && v_scale && o && kv_len, workspace, B, Hq, Hkv, D, Smax, window,
-                              nsplit))
-    return rc;
-  VP_REQUIRE(q_bs % 8 == 0 && k_bs % 16 == 0 && k_ts % 16 == 0 && v_bs % 16 == 0 && v_ts % 16 == 0 &&
-             ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0,
-             VP_ERR_UNSUPPORTED_SHAPE, "vp_decode_attn_kv8: q stride must be a multiple of 8 elements, k / v strides of 16 bytes, bases 16-byte aligned");
-  da_dispatch(D, Hq / Hkv, [&](auto d, auto g) {
-    hipLaunchKernelGGL((decode_attn_split_kv8_kernel<d.value, g.value>), dim3(nsplit, Hkv, B), dim3(256), 0, stream, (const bf16_t*)q, q_bs,
-                       (const uint8_t*)k, k_bs, k_ts, k_scale, ks_bs, ks_ts, (const uint8_t*)v, v_bs, v_ts, v_scale, vs_bs, vs_ts, kv_len,
-                       Smax, window, scale, workspace, Hkv);
-  });
-  hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Hq, B), dim3(D), 0, stream, workspace, (bf16_t*)o, o_bs, Hkv, Hq / Hkv, D, nsplit);
-  return vp_check_launch("vp_decode_attn_kv8");
+  return attn_kv8_run("vp_decode_attn_kv8", B, Hq, Hkv, D, Smax, q, q_bs, k, k_bs, k_ts, k_scale, ks_bs, ks_ts, v, v_bs, v_ts, v_scale,
+                      vs_bs, vs_ts, o, o_bs, kv_len, nullptr, window, scale, nsplit, workspace, stream);
+}
+
+int vp_decode_attn_kv8_rows(int B, int Hq, int Hkv, int D, int Smax, const void* q, long q_bs, const void* k, long k_bs, long k_ts,
+                            const float* k_scale, long ks_bs, long ks_ts, const void* v, long v_bs, long v_ts, const float* v_scale,
+                            long vs_bs, long vs_ts, void* o, long o_bs, const int* kv_len, const int* cache_row, int window, float scale,
+                            int nsplit, float* workspace, hipStream_t stream) {
+  return attn_kv8_run("vp_decode_attn_kv8_rows", B, Hq, Hkv, D, Smax, q, q_bs, k, k_bs, k_ts, k_scale, ks_bs, ks_ts, v, v_bs, v_ts,
+                      v_scale, vs_bs, vs_ts, o, o_bs, kv_len, cache_row, window, scale, nsplit, workspace, stream);
+}
+
+int vp_decode_accept(int B, int n, const int* next, int* tok, int* base_pos, int* pos, int* kv_len, int* n_acc, hipStream_t stream) {
+  VP_REQUIRE(next && tok && base_pos && pos && kv_len && n_acc, VP_ERR_BAD_ARG, "vp_decode_accept: null pointer");
+  VP_REQUIRE(B > 0 && n >= 0 && (long)B * (n + 1) <= (1L << 24), VP_ERR_BAD_ARG, "vp_decode_accept: bad sizes (B %d, n %d)", B, n);
+  hipLaunchKernelGGL(decode_accept_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, next, tok, base_pos, pos, kv_len, n_acc, B,
+                     n);
+  return vp_check_launch("vp_decode_accept");
 }
 
 }  // extern "C"

@@ -13,7 +13,18 @@ _decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when
 After Engine.quantize_decoder() the step streams those matrices as e4m3fn bytes (vp_decode_gemm_w8) or as MXFP4 blocks (vp_decode_gemm_w4)
 instead (quant.py: the contracts); the prefill stays on the bf16 weights, which by then hold exactly the dequantised values.
 Independently of the weights, the cache itself can be kept as e4m3fn bytes with one scale per (token, KV head) (kv_cache_dtype="fp8_e4m3":
-vp_decode_rope_append_kv8 / vp_decode_attn_kv8), or, for verification, as a bf16 cache of the dequantised values read by the bf16 kernels."""
+vp_decode_rope_append_kv8 / vp_decode_attn_kv8), or, for verification, as a bf16 cache of the dequantised values read by the bf16 kernels.
+
+Prompt-lookup decoding (HF generate(prompt_lookup_num_tokens=n, max_matching_ngram_size=g): candidate_generator.py
+PromptLookupCandidateGenerator, greedy only) raises the tokens per step without a second model:
+
+  draft     lookup_draft: the last n-gram of a sequence's tokens is searched earlier in the sequence and what followed it there is proposed
+  verify    one step on B (n + 1) rows: row (b, i) is a batch row of its own at position pos_b + i that appends to and reads sequence b's
+            cache row (the *_rows entry points), so it runs exactly the computation the one-token step would have run for that token:
+            the same GEMM column, the same attention splits (nsplit of B sequences, not of the rows), the same argmax
+  accept    vp_decode_accept keeps the leading drafts that equal the model's own choices and sets the next step's counters; the rows of
+            rejected drafts are overwritten by the next step before anything reads them
+Tokens and logits are those of plain greedy decoding, bit for bit; only the number of steps changes."""
 from __future__ import annotations
 
 import os
@@ -87,6 +98,50 @@ class KVCache:
         return self.lens[self.B:]
 
 
+MAX_VERIFY_ROWS = 16                                             # the skinny GEMMs' M
+
+
+def check_lookup(B, n, do_sample=False, max_ngram=2):
+    """prompt_lookup_num_tokens for B sequences -> n (None / 0: 0 = the plain path).  Host-only, before any GPU work: lookup is greedy
+    (speculative sampling is not built) and a verify step has B (n + 1) <= 16 rows."""
+    n = 0 if n is None else int(n)
+    if n < 0:
+        raise ValueError(f"prompt_lookup_num_tokens = {n}: must be >= 0")
+    if n == 0:
+        return 0
+    if do_sample:
+        raise ValueError("prompt_lookup_num_tokens with do_sample=True: speculative sampling is not built; lookup decoding is greedy "
+                         "(do_sample=False)")
+    if int(max_ngram) < 1:
+        raise ValueError(f"max_matching_ngram_size = {max_ngram}: must be >= 1")
+    if B * (n + 1) > MAX_VERIFY_ROWS:
+        most = MAX_VERIFY_ROWS // B - 1
+        raise ValueError(f"prompt_lookup_num_tokens = {n} at batch {B}: a verify step has B (n + 1) = {B * (n + 1)} rows, the decode GEMMs "
+                         f"take {MAX_VERIFY_ROWS}; the largest prompt_lookup_num_tokens for B = {B} is {max(most, 0)}"
+                         + ("" if most > 0 else " (no lookup at this batch size)"))
+    return n
+
+
+def lookup_draft(history, n, max_ngram=2):
+    """The drafter (HF PromptLookupCandidateGenerator's rule): for g = min(max_ngram, len - 1) down to 1, among the earlier windows equal to
+    the last g tokens of `history` take the EARLIEST one that has a continuation, and return up to n tokens of it; the continuation stops
+    before the first negative id (the <image> placeholder is no embedding row).  No match: [].  history: the sequence's valid prompt ids
+    (attention mask applied) followed by the emitted tokens; plain numpy on the host."""
+    h = np.asarray(history, dtype=np.int64).reshape(-1)
+    L = h.size
+    if int(n) <= 0:
+        return []
+    for g in range(min(int(max_ngram), L - 1), 0, -1):
+        hit = np.flatnonzero((np.lib.stride_tricks.sliding_window_view(h, g) == h[L - g:]).all(1))
+        hit = hit[hit < L - g]                                   # the suffix itself has nothing after it
+        if hit.size:
+            start = int(hit[0]) + g
+            cont = h[start:min(start + int(n), L)]
+            neg = np.flatnonzero(cont < 0)
+            return cont[:int(neg[0])].tolist() if neg.size else cont.tolist()
+    return []
+
+
 def text_plan(eng, input_ids, attention_mask):
     """No-splice prefill input (text-only generate of the PT classes: base_ola_vlm.py:606-607 embeds the tokens as they are): each
     sequence's valid tokens left-aligned in [B*S, H] rows gathered from the embedding table.  Returns (x, plan) with the plan fields
@@ -117,11 +172,15 @@ def text_plan(eng, input_ids, attention_mask):
 
 
 class DecodeSession:
-    """One generate() call: the cache, the preallocated step buffers and (optionally) the captured step."""
+    """One generate() call: the cache, the preallocated step buffers and (optionally) the captured step.
+    lookup = n > 0: verify mode (prompt-lookup decoding).  A step then runs R = B (n + 1) rows, row b (n + 1) + i at position pos_b + i on
+    cache row b, through verify() instead of step(); `steps` and `accepted` count the verify steps and the drafts they accepted."""
 
-    def __init__(self, eng, kv_cache_dtype=None):
+    def __init__(self, eng, kv_cache_dtype=None, lookup=None):
         self.eng = eng
         self.cfg = eng.cfg
+        self.lookup = int(lookup or 0)
+        self.steps = self.accepted = 0
         # the cache format (KVCache): the argument, else the engine's default (model.quantize_kv_cache_for_generation); independent of
         # the weight format below.  Resolved here, on the host, before any GPU work
         self.kv_cache_dtype = resolve_kv_cache_dtype(kv_cache_dtype if kv_cache_dtype is not None else getattr(eng, "kv_cache_dtype", None))
@@ -148,7 +207,7 @@ class DecodeSession:
             x, plan = text_plan(eng, input_ids, attention_mask)
         B, S = plan["B"], plan["S"]
         lens = np.asarray(plan["lens_host"]).astype(np.int64)
-        Smax = int(lens.max()) + int(max_new_tokens)
+        Smax = int(lens.max()) + int(max_new_tokens) + self.lookup     # verify mode: + n rows of slack for rejected drafts
         c = self.cache = KVCache(cfg, B, Smax, eng.dev, self.kv_cache_dtype)
         cw = 2 * nkv * hd
         kvd = self.kv_cache_dtype
@@ -184,6 +243,7 @@ class DecodeSession:
         nqkv = (nh + 2 * nkv) * hd
         V = eng.fz["lm_head"].shape[0]
         e = lambda *shape, dt=BF16: torch.empty(*shape, device=dev, dtype=dt)
+        nseq, B = B, B * (self.lookup + 1)                       # verify mode: every buffer below has one row per verify row
         self.tok = torch.zeros(B, device=dev, dtype=I32)
         self.zeros_b = torch.zeros(B, device=dev, dtype=I32)
         self.x = [e(B, H), e(B, H)]
@@ -196,9 +256,22 @@ class DecodeSession:
                  for q in ((False, True) if self.fq else (False,)))
         self.gws = e(max(1, nb // 4), dt=torch.float32) if nb > 0 else None
         Smax = self.cache.Smax
-        self.nsplit = ops.decode_attn_splits(B, nkv, Smax)
+        self.nsplit = ops.decode_attn_splits(nseq, nkv, Smax)    # of the SEQUENCES: a verify row's splits are the one-token step's
         self.aws = e(ops._lib.raw("vp_decode_attn_workspace_bytes", B, nh, nkv, hd, self.nsplit) // 4, dt=torch.float32)
         self.cos, self.sin = eng.rope(max(Smax, 1))
+        if self.lookup:
+            n1 = self.lookup + 1
+            self.cache_row = torch.arange(nseq, device=dev, dtype=I32).repeat_interleave(n1).contiguous()
+            # row (b, i): pos = pos_b + i, kv_len = pos + 1 (the row's own key included, as on the one-token step); base_pos = the cache's
+            # pos (its kv_len half is not advanced in this mode)
+            lens = torch.from_numpy(self.cache.lens_host.astype(np.int32))
+            rp = (lens[:, None] + torch.arange(n1, dtype=I32)[None]).reshape(-1)
+            self.vlens = torch.cat([rp, rp + 1]).to(dev)
+            self.vpos, self.vkv = self.vlens[:B], self.vlens[B:]
+            self.base_pos = self.cache.pos
+            self.res = torch.zeros(B + nseq, device=dev, dtype=I32)          # next [R] | n_acc [B]: one host read per step
+            self.next32, self.n_acc = self.res[:B], self.res[B:]
+            self.next64 = torch.zeros(B, device=dev, dtype=torch.long)
 
     def _gemm(self, a, key, **kw):
         """One skinny GEMM of the step on weight `key`: its quantised copy when the session decodes from one, else the bf16 weight."""
@@ -220,7 +293,9 @@ class DecodeSession:
         for l in range(cfg.num_hidden_layers):
             o = f"dec.{l}."
             self._gemm(x, o + "wqkv", norm_w=fz[o + "ln1"], eps=eps, out=self.qkv, ws=self.gws)
-            if self.kv_cache_dtype == "fp8_e4m3":
+            if self.lookup:
+                self._attend_rows(l, window)
+            elif self.kv_cache_dtype == "fp8_e4m3":
                 ops.decode_rope_append_kv8(self.qkv, self.q, self.cos, self.sin, c.pos, nh, nkv, hd, k_bytes=c.k(l), v_bytes=c.v(l),
                                            k_scale=c.k_scale(l), v_scale=c.v_scale(l))
                 ops.decode_attn_kv8(self.q, c.k(l), c.v(l), c.k_scale(l), c.v_scale(l), c.kv_len, nh, window=window, nsplit=self.nsplit,
@@ -237,12 +312,39 @@ class DecodeSession:
             self._gemm(self.act, o + "wd", residual=self.h1, out=xn, ws=self.gws)
             x = xn
         self._gemm(x, "lm_head", norm_w=fz["norm"], eps=eps, out_f32=True, out=self.logits, ws=self.gws)
-        ops.add_i32_(c.lens, 1)
+        if self.lookup:                                          # the plain path's argmax (ties break the same way), then the acceptance rule
+            torch.argmax(self.logits, dim=-1, out=self.next64)
+            self.next32.copy_(self.next64)
+            ops.decode_accept(self.next32, self.tok, self.base_pos, self.vpos, self.vkv, self.n_acc, self.lookup)
+        else:
+            ops.add_i32_(c.lens, 1)
+
+    def _attend_rows(self, l, window):
+        """RoPE + append + attention of layer l in verify mode: the plain step's three cache formats through the *_rows entry points."""
+        c, cfg, cr = self.cache, self.cfg, self.cache_row
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        if self.kv_cache_dtype == "fp8_e4m3":
+            ops.decode_rope_append_kv8_rows(self.qkv, self.q, self.cos, self.sin, self.vpos, cr, nh, nkv, hd, k_bytes=c.k(l), v_bytes=c.v(l),
+                                            k_scale=c.k_scale(l), v_scale=c.v_scale(l))
+            ops.decode_attn_kv8_rows(self.q, c.k(l), c.v(l), c.k_scale(l), c.v_scale(l), self.vkv, cr, nh, window=window, nsplit=self.nsplit,
+                                     out=self.att, ws=self.aws)
+            return
+        if self.kv_cache_dtype == "bf16":
+            ops.decode_rope_append_rows(self.qkv, self.q, c.k(l), c.v(l), self.cos, self.sin, self.vpos, cr, nh, nkv, hd)
+        else:                                                   # emulated: the new rows' dequantised values, read by the bf16 kernel
+            ops.decode_rope_append_kv8_rows(self.qkv, self.q, self.cos, self.sin, self.vpos, cr, nh, nkv, hd, k_deq=c.k(l), v_deq=c.v(l))
+        ops.decode_attn_rows(self.q, c.k(l), c.v(l), self.vkv, cr, nh, window=window, nsplit=self.nsplit, out=self.att, ws=self.aws)
 
     def step(self, tokens):
         """Feed one token per sequence (int tensor [B] on the device) -> fp32 logits [B, V] of the next position (a view of a buffer the next
         step overwrites)."""
+        assert not self.lookup, "verify mode steps through verify()"
         self.tok.copy_(tokens.to(I32))
+        self._launch()
+        self.cache.lens_host += 1
+        return self.logits
+
+    def _launch(self):
         if self.use_graph:
             if self.graph is None:
                 self._capture()
@@ -250,8 +352,25 @@ class DecodeSession:
             self.replays += 1
         else:
             self._step_launches()
-        self.cache.lens_host += 1
-        return self.logits
+
+    def feed(self, tokens):
+        """Verify mode: the token of row 0 of every sequence before the FIRST verify step (int [B]); later steps' are set on the device."""
+        self.tok.view(-1, self.lookup + 1)[:, 0].copy_(tokens.to(I32))
+
+    def verify(self, drafts):
+        """One verify step.  drafts: int32 [B, n] on the host, the tokens of rows 1 .. n of every sequence (any valid embedding row: a draft
+        counts only if it equals the model's own token).  -> (next [B, n + 1], n_acc [B]) on the host: the model's choice at every row and
+        the number of drafts accepted; sequence b emitted next[b, 0 .. n_acc[b]].  `logits` [B (n + 1), V] holds the rows they were chosen
+        from until the next step."""
+        n1 = self.lookup + 1
+        self.tok.view(-1, n1)[:, 1:].copy_(drafts.to(I32))
+        self._launch()
+        res = self.res.cpu()                                     # the step's one host read
+        nxt, n_acc = res[:self.tok.numel()].view(-1, n1), res[self.tok.numel():]
+        self.steps += 1
+        self.accepted += int(n_acc.sum())
+        self.cache.lens_host += n_acc.numpy().astype(np.int64) + 1
+        return nxt, n_acc
 
     def _capture(self):
         """Capture _step_launches once (single stream, no fork).  Capture records without executing; `lens` moves only on replay."""
@@ -286,11 +405,18 @@ def next_tokens(logits, do_sample=False, temperature=1.0, top_p=1.0, generator=N
 
 def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=20, do_sample=False, temperature=1.0,
              top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False,
-             kv_cache_dtype=None):
+             kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, drafter=None):
     """Greedy / sampled decoding of B prompts, each continuing at its own length -> LongTensor [B, n_new] of the new tokens only (rows that
     finished are padded with pad_token_id after their EOS).  return_logits: also the fp32 logits [B, V] each token was chosen from.
-    kv_cache_dtype: None (the engine's default, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" (KVCache)."""
+    kv_cache_dtype: None (the engine's default, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" (KVCache).
+    prompt_lookup_num_tokens = n > 0 (HF's argument; greedy only, B (n + 1) <= 16): prompt-lookup decoding with n drafts per step from
+    lookup_draft(history, n, max_matching_ngram_size), or from drafter(b, history) -> list of ids (no HF argument: the test and benchmark
+    hook).  The result, the streamer calls and the logits are those of the plain path."""
     B = input_ids.shape[0]
+    lookup = check_lookup(B, prompt_lookup_num_tokens, do_sample, max_matching_ngram_size)
+    if lookup:
+        return _generate_lookup(eng, input_ids, attention_mask, images, group_sizes, int(max_new_tokens), eos_token_id, pad_token_id, streamer,
+                                use_graph, return_logits, kv_cache_dtype, lookup, int(max_matching_ngram_size), drafter)
     eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
     if pad_token_id is None:
         pad_token_id = eos[0] if eos else 0
@@ -324,6 +450,82 @@ def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None,
     if streamer is not None:
         streamer.end()
     res = torch.stack(out, 1) if out else torch.empty(B, 0, dtype=torch.long, device=eng.dev)
+    sess.graph = None
+    if return_logits:
+        return res, kept, sess
+    return res
+
+
+def _generate_lookup(eng, input_ids, attention_mask, images, group_sizes, N, eos_token_id, pad_token_id, streamer, use_graph, return_logits,
+                     kv_cache_dtype, n, max_ngram, drafter):
+    """generate() with prompt-lookup decoding.  Every sequence keeps its own list of raw (greedy) tokens, which a verify step extends by
+    1 + accepted drafts; output column i (EOS / pad handling, streamer.put, the kept logits) is produced as soon as every sequence has its
+    token i, by the plain loop's rules, so the result is the plain path's whatever the drafts were."""
+    B = input_ids.shape[0]
+    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
+    if pad_token_id is None:
+        pad_token_id = eos[0] if eos else 0
+    sess = DecodeSession(eng, kv_cache_dtype, lookup=n)
+    if use_graph is not None:
+        sess.use_graph = bool(use_graph)
+    if streamer is not None:
+        streamer.put(input_ids.cpu())
+    ids = input_ids.detach().cpu().numpy().astype(np.int64)
+    am = np.ones_like(ids, dtype=bool) if attention_mask is None else attention_mask.detach().cpu().numpy().astype(bool)
+    prompt = [ids[b][am[b]] for b in range(B)]
+    V = eng.fz["embed"].shape[0]
+    if drafter is None:
+        drafter = lambda b, history: lookup_draft(history, n, max_ngram)
+    dev = eng.dev
+    out, kept = [], []
+    raw = [[] for _ in range(B)]                                 # the greedy tokens of every sequence, pad-free
+    rows = [[] for _ in range(B)]                                # return_logits: the logits row each of them was chosen from
+    finished = [False] * B
+    done = N <= 0
+
+    def flush():
+        nonlocal done
+        while not done and len(out) < min(len(r) for r in raw):
+            i = len(out)
+            col = [pad_token_id if finished[b] else raw[b][i] for b in range(B)]
+            nxt = torch.tensor(col, dtype=torch.long, device=dev)
+            out.append(nxt)
+            if return_logits:
+                kept.append(torch.stack([rows[b][i] for b in range(B)]))
+            if streamer is not None:
+                streamer.put(nxt.cpu())
+            if eos:
+                for b in range(B):
+                    finished[b] = finished[b] or col[b] in eos
+            done = len(out) >= N or (bool(eos) and all(finished))
+
+    with torch.no_grad():
+        if not done:
+            logits = sess.prefill(input_ids, attention_mask, images, group_sizes, N)
+            first = torch.argmax(logits, dim=-1)
+            sess.feed(first)
+            for b, t in enumerate(first.tolist()):
+                raw[b].append(t)
+                if return_logits:
+                    rows[b].append(logits[b].clone())
+            flush()
+        drafts = torch.empty(B, n, dtype=I32)
+        while not done:
+            for b in range(B):
+                d = [int(t) for t in drafter(b, np.concatenate([prompt[b], np.asarray(raw[b], np.int64)]))][:n]
+                bad = [j for j, t in enumerate(d) if not 0 <= t < V]
+                d = d[:bad[0]] if bad else d                     # a draft is an embedding row; what follows an invalid one is dropped with it
+                drafts[b] = torch.tensor(d + [raw[b][-1]] * (n - len(d)), dtype=I32)     # unused slots: the row-0 token (harmless)
+            nxt, n_acc = sess.verify(drafts)
+            for b in range(B):
+                k = int(n_acc[b]) + 1
+                raw[b].extend(nxt[b, :k].tolist())
+                if return_logits:
+                    rows[b].extend(sess.logits[b * (n + 1):b * (n + 1) + k].clone().unbind(0))
+            flush()
+    if streamer is not None:
+        streamer.end()
+    res = torch.stack(out, 1) if out else torch.empty(B, 0, dtype=torch.long, device=dev)
     sess.graph = None
     if return_logits:
         return res, kept, sess

@@ -145,6 +145,12 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
     kv_cache_dtype = kwargs.pop("kv_cache_dtype", None)
     if kv_cache_dtype is not None:
         kv_cache_dtype = decode.resolve_kv_cache_dtype(kv_cache_dtype)
+    # prompt-lookup decoding (HF's two arguments; max_matching_ngram_size None = HF's default of 2): refused here, on the host, where it
+    # cannot run (sampling, more than 16 verify rows)
+    lookup = kwargs.pop("prompt_lookup_num_tokens", None)
+    max_ngram = kwargs.pop("max_matching_ngram_size", None)
+    max_ngram = 2 if max_ngram is None else int(max_ngram)
+    lookup = decode.check_lookup(inputs.shape[0], lookup, do_sample, max_ngram)
     with torch.no_grad():
         module._sync_trainable()
         eng = module._get_engine()
@@ -158,7 +164,8 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
             pad_token_id = getattr(module.config, "pad_token_id", None)
         return decode.generate(eng, inputs, attention_mask, images, gsz, max_new_tokens=max_new_tokens, do_sample=do_sample,
                                temperature=temperature, top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                               streamer=streamer, generator=generator, kv_cache_dtype=kv_cache_dtype)
+                               streamer=streamer, generator=generator, kv_cache_dtype=kv_cache_dtype,
+                               prompt_lookup_num_tokens=lookup, max_matching_ngram_size=max_ngram)
 
 
 class _VisperStep(torch.autograd.Function):
@@ -592,12 +599,14 @@ class _OlaCausalLMBase(OlaLlavaMetaForCausalLM, BaseOLA_VLM, EngineModule):
 
     def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
                  top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None,
-                 kv_cache_dtype=None, **kwargs):
+                 kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kwargs):
         """base_ola_vlm.py:579-616: with `images` the prompt is spliced (image features + task tokens, ola_arch.py:256-444); with
         images=None it is the token embeddings alone (base_ola_vlm.py:606-607).  -> LongTensor [B, n_new] (new tokens only).
-        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated"."""
+        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated".
+        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps)."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
-                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype, **kwargs)
+                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype,
+                         prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, **kwargs)
 
 
 class OlaLlavaLlamaForCausalLM(_OlaCausalLMBase):

@@ -152,12 +152,14 @@ class _LlavaCausalLMBase(LlavaMetaForCausalLM, EngineModule):
 
     def generate(self, inputs=None, images=None, image_sizes=None, attention_mask=None, max_new_tokens=20, do_sample=False, temperature=1.0,
                  top_p=1.0, eos_token_id=None, pad_token_id=None, num_beams=1, use_cache=True, streamer=None, generator=None,
-                 kv_cache_dtype=None, **kwargs):
+                 kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, **kwargs):
         """llava_llama.py:122-153: images -> prepare_inputs_labels_for_multimodal's splice, else the token embeddings alone; then HF
         generation over inputs_embeds.  -> LongTensor [B, n_new] (new tokens only).
-        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated"."""
+        kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated".
+        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps)."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
-                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype, **kwargs)
+                         pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype,
+                         prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, **kwargs)
 
 
 class LlavaLlamaForCausalLM(_LlavaCausalLMBase):

@@ -726,7 +726,17 @@ def quant_blocks_mxfp4(w, writeback=False):
     return q, e
 
 
-def decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv, D):
+def _row_map(cache_row, B, cache_rows):
+    """The trailing pointer of a *_rows entry point: int32 [B] on the device, or None (identity: the cache then needs B rows).  Its values
+    must lie in [0, cache_rows): the caller's contract, not checked here (a device read)."""
+    if cache_row is None:
+        assert cache_rows >= B, (cache_rows, B)
+        return (None,)
+    assert cache_row.dtype == torch.int32 and cache_row.is_contiguous() and cache_row.numel() == B, (cache_row.shape, cache_row.dtype, B)
+    return (_p(cache_row),)
+
+
+def decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv, D, _rows=None):
     """RoPE of one new token per sequence at position pos[b] (int32 [B], device): q -> q_out [B, Hq*D]; k, v -> row pos[b] of the caches
     ([B, Smax, Hkv, D] views whose (Hkv, D) block is contiguous)."""
     B, _, ldqkv = _rows2d(qkv)
@@ -734,9 +744,17 @@ def decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv,
     vb, vt = _bshd(v_cache)
     Smax = k_cache.shape[1]
     assert cos_t.shape[0] >= Smax and pos.dtype == torch.int32 and pos.numel() == B
-    _lib.call("vp_decode_rope_append", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out), q_out.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt,
-              _p(cos_t), _p(sin_t), _p(pos), Smax, _stream())
+    _lib.call("vp_decode_rope_append" if _rows is None else "vp_decode_rope_append_rows", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out),
+              q_out.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt, _p(cos_t), _p(sin_t), _p(pos), *(_rows or ()), Smax, _stream())
     return q_out
+
+
+def decode_rope_append_rows(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, cache_row, Hq, Hkv, D):
+    """decode_rope_append with a row map (vp_decode_rope_append_rows): row r of qkv is appended at position pos[r] of cache row
+    cache_row[r] (int32 [B] on the device; None = identity); q_out stays indexed by r.  Several rows may share a cache row at different
+    positions (the n + 1 rows of a prompt-lookup verify step); equal (cache_row, pos) pairs are not allowed."""
+    return decode_rope_append(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos, Hq, Hkv, D,
+                              _rows=_row_map(cache_row, qkv.shape[0], k_cache.shape[0]))
 
 
 def decode_attn_splits(B, Hkv, Smax, cus=256):
@@ -746,8 +764,10 @@ def decode_attn_splits(B, Hkv, Smax, cus=256):
 
 
 def _decode_attn_defaults(q, cache, Hq, scale, nsplit, out, ws):
-    """(scale, nsplit, out, ws) of decode_attn / decode_attn_kv8 with the caller's None filled in; cache [B, Smax, Hkv, D]."""
-    B, Smax, Hkv, D = cache.shape
+    """(scale, nsplit, out, ws) of decode_attn / decode_attn_kv8 with the caller's None filled in; cache [B, Smax, Hkv, D] (with a row map:
+    any number of cache rows; B is q's)."""
+    _, Smax, Hkv, D = cache.shape
+    B = q.shape[0]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if nsplit is None:
@@ -759,15 +779,26 @@ def _decode_attn_defaults(q, cache, Hq, scale, nsplit, out, ws):
     return scale, nsplit, out, ws
 
 
-def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+def decode_attn(q, k_cache, v_cache, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None, _rows=None):
     """q [B, Hq*D] rows, caches [B, Smax, Hkv, D], kv_len int32 [B] (device) -> o [B, Hq*D] bf16."""
     B, Smax, Hkv, D = k_cache.shape
+    if _rows is not None:
+        B = q.shape[0]
+    assert q.shape[0] == B and kv_len.numel() == B, (q.shape, kv_len.shape, B)
     scale, nsplit, out, ws = _decode_attn_defaults(q, k_cache, Hq, scale, nsplit, out, ws)
     kb, kt = _bshd(k_cache)
     vb, vt = _bshd(v_cache)
-    _lib.call("vp_decode_attn", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_cache), kb, kt, _p(v_cache), vb, vt, _p(out), out.stride(0),
-              _p(kv_len), int(window), float(scale), int(nsplit), _p(ws), _stream())
+    _lib.call("vp_decode_attn" if _rows is None else "vp_decode_attn_rows", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_cache), kb, kt,
+              _p(v_cache), vb, vt, _p(out), out.stride(0), _p(kv_len), *(_rows or ()), int(window), float(scale), int(nsplit), _p(ws),
+              _stream())
     return out
+
+
+def decode_attn_rows(q, k_cache, v_cache, kv_len, cache_row, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+    """decode_attn with a row map (vp_decode_attn_rows): query row r attends to keys 0 .. kv_len[r] - 1 of cache row cache_row[r] (int32 [B]
+    on the device; None = identity).  nsplit None: decode_attn_splits of q's row count; pass the one-token session's value to reproduce its
+    rows bit for bit."""
+    return decode_attn(q, k_cache, v_cache, kv_len, Hq, window, scale, nsplit, out, ws, _rows=_row_map(cache_row, q.shape[0], k_cache.shape[0]))
 
 
 def quant_kv_e4m3(src, D, q_out=None, scale_out=None, deq_out=None):
@@ -798,7 +829,7 @@ def _bsh(t):
 
 
 def decode_rope_append_kv8(qkv, q_out, cos_t, sin_t, pos, Hq, Hkv, D, k_bytes=None, v_bytes=None, k_scale=None, v_scale=None, k_deq=None,
-                           v_deq=None):
+                           v_deq=None, _rows=None):
     """decode_rope_append for the FP8 KV cache (vp_decode_rope_append_kv8): q -> q_out as there (bit-identical); row pos[b] of the byte
     caches (uint8 [B, Smax, Hkv, D] views) and of the scales (fp32 [B, Smax, Hkv] views) receives the quantised rotated k and the quantised
     v, and / or row pos[b] of the bf16 caches k_deq / v_deq their dequantised values."""
@@ -806,37 +837,69 @@ def decode_rope_append_kv8(qkv, q_out, cos_t, sin_t, pos, Hq, Hkv, D, k_bytes=No
     bytes_, deq = k_bytes is not None, k_deq is not None
     assert bytes_ or deq, "a byte cache and / or a bf16 cache"
     a = [None, 0, 0] * 6
-    Smax = (k_bytes if bytes_ else k_deq).shape[1]
+    Bc, Smax = (k_bytes if bytes_ else k_deq).shape[:2]          # cache rows: B itself without a row map
+    assert _rows is not None or Bc == B, (Bc, B)
     if bytes_:
         for t in (k_bytes, v_bytes):
-            assert t.dtype == torch.uint8 and tuple(t.shape) == (B, Smax, Hkv, D), (t.shape, t.dtype)
+            assert t.dtype == torch.uint8 and tuple(t.shape) == (Bc, Smax, Hkv, D), (t.shape, t.dtype)
         for t in (k_scale, v_scale):
-            assert t.dtype == torch.float32 and tuple(t.shape) == (B, Smax, Hkv), (t.shape, t.dtype)
+            assert t.dtype == torch.float32 and tuple(t.shape) == (Bc, Smax, Hkv), (t.shape, t.dtype)
         a[0:12] = [_p(k_bytes), *_bshd(k_bytes), _p(v_bytes), *_bshd(v_bytes), _p(k_scale), *_bsh(k_scale), _p(v_scale), *_bsh(v_scale)]
     if deq:
         for t in (k_deq, v_deq):
-            assert t.dtype == BF16 and tuple(t.shape) == (B, Smax, Hkv, D), (t.shape, t.dtype)
+            assert t.dtype == BF16 and tuple(t.shape) == (Bc, Smax, Hkv, D), (t.shape, t.dtype)
         a[12:18] = [_p(k_deq), *_bshd(k_deq), _p(v_deq), *_bshd(v_deq)]
     assert cos_t.shape[0] >= Smax and pos.dtype == torch.int32 and pos.numel() == B
-    _lib.call("vp_decode_rope_append_kv8", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out), q_out.stride(0), *a, _p(cos_t), _p(sin_t), _p(pos), Smax,
-              _stream())
+    _lib.call("vp_decode_rope_append_kv8" if _rows is None else "vp_decode_rope_append_kv8_rows", B, Hq, Hkv, D, _p(qkv), ldqkv, _p(q_out),
+              q_out.stride(0), *a, _p(cos_t), _p(sin_t), _p(pos), *(_rows or ()), Smax, _stream())
     return q_out
 
 
-def decode_attn_kv8(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+def decode_rope_append_kv8_rows(qkv, q_out, cos_t, sin_t, pos, cache_row, Hq, Hkv, D, k_bytes=None, v_bytes=None, k_scale=None, v_scale=None,
+                                k_deq=None, v_deq=None):
+    """decode_rope_append_kv8 with a row map (vp_decode_rope_append_kv8_rows): bytes, scales and / or dequantised rows of qkv row r go to
+    position pos[r] of cache row cache_row[r] (decode_rope_append_rows: the same contract)."""
+    Bc = (k_bytes if k_bytes is not None else k_deq).shape[0]
+    return decode_rope_append_kv8(qkv, q_out, cos_t, sin_t, pos, Hq, Hkv, D, k_bytes, v_bytes, k_scale, v_scale, k_deq, v_deq,
+                                  _rows=_row_map(cache_row, qkv.shape[0], Bc))
+
+
+def decode_attn_kv8(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, Hq, window=0, scale=None, nsplit=None, out=None, ws=None, _rows=None):
     """decode_attn on the FP8 KV cache (vp_decode_attn_kv8): q [B, Hq*D] rows, byte caches uint8 [B, Smax, Hkv, D], scales fp32
     [B, Smax, Hkv], kv_len int32 [B] (device) -> o [B, Hq*D] bf16.  Same splits and workspace as decode_attn."""
     B, Smax, Hkv, D = k_bytes.shape
     assert k_bytes.dtype == torch.uint8 and v_bytes.dtype == torch.uint8 and tuple(v_bytes.shape) == (B, Smax, Hkv, D)
     assert k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32 and tuple(k_scale.shape) == tuple(v_scale.shape) == (B, Smax, Hkv)
+    if _rows is not None:
+        B = q.shape[0]
+    assert q.shape[0] == B and kv_len.numel() == B, (q.shape, kv_len.shape, B)
     scale, nsplit, out, ws = _decode_attn_defaults(q, k_bytes, Hq, scale, nsplit, out, ws)
     kb, kt = _bshd(k_bytes)
     vb, vt = _bshd(v_bytes)
     ksb, kst = _bsh(k_scale)
     vsb, vst = _bsh(v_scale)
-    _lib.call("vp_decode_attn_kv8", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_bytes), kb, kt, _p(k_scale), ksb, kst, _p(v_bytes), vb, vt,
-              _p(v_scale), vsb, vst, _p(out), out.stride(0), _p(kv_len), int(window), float(scale), int(nsplit), _p(ws), _stream())
+    _lib.call("vp_decode_attn_kv8" if _rows is None else "vp_decode_attn_kv8_rows", B, Hq, Hkv, D, Smax, _p(q), q.stride(0), _p(k_bytes), kb,
+              kt, _p(k_scale), ksb, kst, _p(v_bytes), vb, vt, _p(v_scale), vsb, vst, _p(out), out.stride(0), _p(kv_len), *(_rows or ()),
+              int(window), float(scale), int(nsplit), _p(ws), _stream())
     return out
+
+
+def decode_attn_kv8_rows(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, cache_row, Hq, window=0, scale=None, nsplit=None, out=None, ws=None):
+    """decode_attn_kv8 with a row map (vp_decode_attn_kv8_rows; decode_attn_rows: the same contract)."""
+    return decode_attn_kv8(q, k_bytes, v_bytes, k_scale, v_scale, kv_len, Hq, window, scale, nsplit, out, ws,
+                           _rows=_row_map(cache_row, q.shape[0], k_bytes.shape[0]))
+
+
+def decode_accept(next_tok, tok, base_pos, pos, kv_len, n_acc, n):
+    """The acceptance rule of a prompt-lookup verify step and the next step's counters (vp_decode_accept), all int32 on the device:
+    next_tok [B (n + 1)] = the argmax of every row, tok [B (n + 1)] = what the rows were fed (row (b, 0) the last emitted token, rows
+    (b, 1 .. n) the drafts), base_pos / n_acc [B], pos / kv_len [B (n + 1)].  In place: n_acc[b] = the number of leading drafts the model
+    itself chose, base_pos[b] += n_acc[b] + 1, pos[b, i] = base_pos[b] + i, kv_len = pos + 1, tok[b, 0] = next_tok[b, n_acc[b]]."""
+    B, R = base_pos.numel(), base_pos.numel() * (int(n) + 1)
+    for t, m in ((next_tok, R), (tok, R), (pos, R), (kv_len, R), (base_pos, B), (n_acc, B)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == m, (t.shape, t.dtype, m)
+    _lib.call("vp_decode_accept", B, int(n), _p(next_tok), _p(tok), _p(base_pos), _p(pos), _p(kv_len), _p(n_acc), _stream())
+    return n_acc
 
 
 def add_i32_(x, delta=1):
