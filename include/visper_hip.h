@@ -220,7 +220,7 @@ int vp_attn_bwd_rope(int B, int Hq, int Hkv, int Sq, int Skv, int D, const void*
  *   weight (interleaved 8-row chunks as ops.interleave_gate_up lays it out / [gate | up] halves), C = silu(gate) * up [M, N/2].  Shapes whose
  *   N has too few 16-row tiles to fill the chip also split K over blocks: `workspace` = vp_decode_gemm_workspace_bytes(M, N, K, epilogue)
  *   bytes of caller-owned device memory (0 = none needed; NULL then allowed), summed in a fixed order (bit-identical run to run).
- *   K, lda, ldw multiples of 8, A / W / norm_w 16-byte aligned. */
+ *   K, lda, ldw multiples of 8, A / W / norm_w 16-byte aligned.  17 <= M <= 64: vp_decode_gemm_wide below. */
 #define VP_EPI_SWIGLU_IL 4
 #define VP_EPI_SWIGLU_HALVES 5
 long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue);
@@ -262,6 +262,23 @@ long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue);
 int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       vp_stream_t stream);
+/* 17 .. 64 sequences per step.  vp_decode_gemm_wide / _w8_wide / _w4_wide: their parents for 1 <= M <= 64, with the parents' argument lists,
+ * shape and alignment rules, split-K contract (their own *_wide_workspace_bytes(M, N, K, epilogue): the slabs, nothing else) and error codes.
+ * A block still streams one 16-row W tile once and serves up to four 16-row A tiles from each converted W fragment, so the weight bytes of
+ * a step do not grow with M.  Output row m is a function of A row m alone: it equals, bit for bit, what the parent returns for that row
+ * inside any 16-row slice of A (calling the parent once per slice is the same computation that reads W once per slice).  M <= 16 launches
+ * the parent's kernel.  The RMSNorm prologue stays inside the kernel (every block computes the rstd of all M rows). */
+long vp_decode_gemm_wide_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual,
+                        long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, vp_stream_t stream);
+long vp_decode_gemm_w8_wide_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm_w8_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
+                           const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                           vp_stream_t stream);
+long vp_decode_gemm_w4_wide_workspace_bytes(int M, int N, int K, int epilogue);
+int vp_decode_gemm_w4_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C,
+                           long ldc, const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32,
+                           float* workspace, vp_stream_t stream);
 /* RoPE of the new token and the KV append (HF apply_rotary_pos_emb + DynamicCache.update, modeling_llama.py, at position pos[b] of each
  * sequence): qkv [B, ldqkv] rows (Hq q heads | Hkv k heads | Hkv v heads, head_dim D); q rotated into q_out [B, ldq]; k rotated and v copied
  * into row pos[b] of the caches ([B, Smax, Hkv, D] views, strides in elements).  cos_t / sin_t: fp32 [>= Smax, D/2] (ops.rope_tables); pos:

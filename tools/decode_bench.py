@@ -36,6 +36,15 @@ tool asserts that both lookup legs reproduce the plain leg's tokens.  Batch size
 profiles/decode_bench_{llama3,phi3}_lookup.json.
 
   python tools/decode_bench.py --model llama3 --lookup 7 --batches 1
+
+--wide: 17 .. 64 sequences per step at the chosen --weights (the engine stays in that format).  Per batch size (default 16,32,64) the wide
+leg (one vp_decode_gemm*_wide call per GEMM) and the chunked leg (DecodeSession.wide_gemm = False: the M <= 16 entry point once per 16-row
+slice) alternate, --repeats runs each, in one process on the same engine and prompts; at B = 16 both legs are the M <= 16 kernel (the
+yardstick of the run-to-run spread).  The prompt is --text tokens + one image; where a batch does not fit, the text is shortened by a
+quarter until it does, and every run records the text_tokens it used.  A cell is a "gain" only if the slowest wide run lies below the
+fastest chunked run.  Default --out: profiles/decode_bench_{llama3,phi3}_wide.json, which collects the cells of every --weights run.
+
+  python tools/decode_bench.py --model llama3 --wide --weights mxfp4
 """
 import argparse
 import json
@@ -72,11 +81,12 @@ def prompt(eng, B, text_tokens, seed=0):
     return ids, images
 
 
-def time_decode(eng, B, new, text_tokens, use_graph, kv=None):
+def time_decode(eng, B, new, text_tokens, use_graph, kv=None, wide=None):
     from visper_lm_amd import decode
     ids, images = prompt(eng, B, text_tokens)
     sess = decode.DecodeSession(eng, kv_cache_dtype=kv)
     sess.use_graph = use_graph
+    sess.wide_gemm = wide
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     logits = sess.prefill(ids, None, images, None, new + 1)
@@ -171,6 +181,35 @@ def kv_legs(eng, weights, B, new, text_tokens, repeats, use_graph):
                 slowest_kv_fp8=max(t["fp8"]), fastest_kv_bf16=min(t["bf16"]), verdict="gain" if gain else "no gain",
                 kv_bf16_cache_bytes=cb["bf16"], kv_fp8_cache_bytes=cb["fp8"], kv_fp8_over_kv_bf16_bytes=round(cb["fp8"] / cb["bf16"], 4),
                 runs=legs["bf16"] + legs["fp8"])
+
+
+def wide_legs(eng, weights, B, new, text_tokens, repeats, use_graph):
+    """wide and chunked legs alternately on one engine -> dict with every run, ms per step and tokens per second of both legs, the verdict"""
+    legs = {"wide": [], "chunked": []}
+    for _ in range(repeats):
+        for leg in legs:
+            while True:
+                try:
+                    r = time_decode(eng, B, new, text_tokens, use_graph, wide=None if leg == "wide" else False)
+                    break
+                except torch.cuda.OutOfMemoryError:
+                    torch.cuda.empty_cache()
+                    text_tokens = text_tokens * 3 // 4                   # the longest prompt that fits, to a quarter
+                    if text_tokens < 16:
+                        raise
+            r.update(weights=weights, leg=leg, text_tokens=text_tokens, tokens_per_s=round(B / r["ms_per_token"] * 1e3, 1))
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    t = {k: [r["ms_per_token"] for r in v] for k, v in legs.items()}
+    texts = sorted({r["text_tokens"] for v in legs.values() for r in v})
+    gain = max(t["wide"]) < min(t["chunked"])
+    return dict(weights=weights, B=B, a_tiles=(B + 15) // 16, graph=use_graph, repeats=repeats, prompt=f"1 image + {texts[0]} text tokens",
+                same_prompt_in_every_run=len(texts) == 1, prompt_rows=legs["wide"][-1]["prompt_rows"],
+                wide_ms_per_step=t["wide"], chunked_ms_per_step=t["chunked"], wide_median=med(t["wide"]), chunked_median=med(t["chunked"]),
+                wide_tokens_per_s=round(B / med(t["wide"]) * 1e3, 1), chunked_tokens_per_s=round(B / med(t["chunked"]) * 1e3, 1),
+                wide_over_chunked=round(med(t["wide"]) / med(t["chunked"]), 4), slowest_wide=max(t["wide"]), fastest_chunked=min(t["chunked"]),
+                verdict=("same kernel" if B <= 16 else "gain" if gain else "no gain"), runs=legs["wide"] + legs["chunked"])
 
 
 def time_lookup(eng, B, new, text_tokens, use_graph, kv, n, leg, ref):
@@ -278,8 +317,14 @@ def main():
                     help="fp8: at the chosen --weights, bf16-cache and fp8-cache legs alternately on one engine, --repeats runs each")
     ap.add_argument("--lookup", type=int, default=0,
                     help="N > 0: prompt-lookup decoding with N drafts per step: plain, always-wrong and always-right legs, --repeats runs each")
+    ap.add_argument("--wide", action="store_true",
+                    help="wide (one call) and chunked (16-row slices) GEMM legs alternately at B = 16, 32, 64 (--batches), --repeats runs each")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.wide:
+        a.out = a.out or os.path.join(ROOT, "profiles", f"decode_bench_{a.model}_wide.json")
+        if a.batches == "1,8":
+            a.batches = "16,32,64"
     if a.lookup and not a.out:
         a.out = os.path.join(ROOT, "profiles", f"decode_bench_{a.model}_lookup.json")
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
@@ -287,6 +332,27 @@ def main():
     dec_b, head_b = weight_bytes(eng)
     res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
                roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
+    if a.wide:
+        if a.weights != "bf16":
+            eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")
+        res.update(wide=True, lm_head_quantised_with_the_decoder=True, cells=[])
+        if os.path.exists(a.out):                                 # the file collects the formats: this run replaces its own cells only
+            old = json.load(open(a.out))
+            if old.get("wide") and old.get("model") == a.model and old.get("layers") == res["layers"]:
+                res["cells"] = [c for c in old["cells"] if c["weights"] != a.weights]
+                res["runs"] = [r for r in old["runs"] if r["weights"] != a.weights]
+        for B in [int(x) for x in a.batches.split(",")]:
+            if a.profile:                                         # kernel-trace run: the wide leg alone, eager launches
+                r = time_decode(eng, B, a.new, a.text, False)
+                r.update(weights=a.weights, leg="wide")
+                print(json.dumps(r), flush=True)
+                continue
+            cell = wide_legs(eng, a.weights, B, a.new, a.text, a.repeats, a.graph)
+            res["runs"] += cell.pop("runs")
+            res["cells"].append(cell)
+        if a.profile:
+            return
+        a.weights = a.kv = "wide"                                 # the other modes below do not run
     if a.lookup:
         if a.weights != "bf16":
             eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")

@@ -77,6 +77,13 @@ _SIGS = {
     "vp_quant_blocks_mxfp4": [i, i, p, l, p, l, p, l, i, p],
     "vp_decode_gemm_w4_workspace_bytes": [i, i, i, i],
     "vp_decode_gemm_w4": [i, i, i, p, l, p, l, p, l, p, l, p, l, p, f, i, i, p, p],
+    # 17 .. 64 sequences per step: the three GEMMs on up to four 16-row A tiles per streamed weight tile (argument lists of their parents)
+    "vp_decode_gemm_wide_workspace_bytes": [i, i, i, i],
+    "vp_decode_gemm_wide": [i, i, i, p, l, p, l, p, l, p, l, p, f, i, i, p, p],
+    "vp_decode_gemm_w8_wide_workspace_bytes": [i, i, i, i],
+    "vp_decode_gemm_w8_wide": [i, i, i, p, l, p, l, p, p, l, p, l, p, f, i, i, p, p],
+    "vp_decode_gemm_w4_wide_workspace_bytes": [i, i, i, i],
+    "vp_decode_gemm_w4_wide": [i, i, i, p, l, p, l, p, l, p, l, p, l, p, f, i, i, p, p],
     "vp_decode_rope_append": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, p, p, i, p],
     "vp_decode_attn_workspace_bytes": [i, i, i, i, i],
     "vp_decode_attn": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, p, i, f, i, p, p],
@@ -110,7 +117,8 @@ _SIGS = {
     "vp_comm_destroy": [p],
 }
 _RET_LONG = {"vp_emb_loss_workspace", "vp_gemm_sched_workspace_bytes", "vp_emb_loss_counter_bytes", "vp_decode_gemm_workspace_bytes",
-             "vp_decode_attn_workspace_bytes", "vp_decode_gemm_w8_workspace_bytes", "vp_decode_gemm_w4_workspace_bytes"}
+             "vp_decode_attn_workspace_bytes", "vp_decode_gemm_w8_workspace_bytes", "vp_decode_gemm_w4_workspace_bytes",
+             "vp_decode_gemm_wide_workspace_bytes", "vp_decode_gemm_w8_wide_workspace_bytes", "vp_decode_gemm_w4_wide_workspace_bytes"}
 EXPORTS = ["vp_last_error_string"] + list(_SIGS)
 # measurement / development entry points (include/visper_hip_debug.h): present only in a -DVP_DEBUG build; bound when the library has them
 _DEBUG_SIGS = {

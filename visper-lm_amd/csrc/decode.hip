@@ -8,6 +8,8 @@
 //    loaded: vp_rmsnorm_fwd's rounding points), epilogues: none (bf16 / fp32 out), + residual, SwiGLU (act written directly).  Each format
 //    owns its chunk loop (hand-shaped loads, waits and registers); argument block, split rule, prologue, reduction, epilogue, combine and
 //    the host side (dg_run) are one piece of code for the three.
+//  - decode_gemm_wide_kernel / decode_gemm_w8_wide_kernel / decode_gemm_w4_wide_kernel: the same blocks for 17 <= M <= 64 rows: up to four
+//    16-row A tiles per streamed W tile, every output row bit-equal to the kernels above on that row.
 //  - decode_rope_append_kernel / decode_rope_append_kv8_kernel: rotate-half RoPE of q / k at per-sequence positions pos[b] (vp_rope's
 //    rounding points), k / v appended to row pos[b] of the bf16 | e4m3 cache.
 //  - the *_rows entry points of the append and attention kernels: the same kernels with a row map (cache_row[r] = the cache row that batch
@@ -93,8 +95,9 @@ __device__ __forceinline__ void dg_rstd_rows(const DecGemmArgs& p, int w, int la
 }
 
 // the 4 waves' accumulators -> one 16 x 16 tile in a fixed order, then the fp32 slab of split ks (KS > 1: unscaled) or the epilogue.
+// M0: the A row of the tile's column 0 (the wide kernels' 16-row A tiles; 0 in the M <= 16 kernels).
 // ROWSCALE (W8): W row n's sum is multiplied by wscale[n] before dg_store's first rounding point
-template <bool ROWSCALE>
+template <bool ROWSCALE, int M0 = 0>
 __device__ __forceinline__ void dg_reduce_store(const DecGemmArgs& p, f32x4 acc, int t, int ks, int w, int lane, float (*red)[256],
                                                 float (*tile_s)[17]) {
 #pragma unroll
@@ -106,22 +109,22 @@ __device__ __forceinline__ void dg_reduce_store(const DecGemmArgs& p, f32x4 acc,
     tile_s[(l2 >> 4) * 4 + i][l2 & 15] = s;                      // C fragment: row (n) = (lane >> 4) * 4 + reg, col (m) = lane & 15
   }
   __syncthreads();
-  const int nl = threadIdx.x >> 4, mm = threadIdx.x & 15;
+  const int nl = threadIdx.x >> 4, ml = threadIdx.x & 15, mm = M0 + ml;
   if (p.KS > 1) {                                                // fp32 slab [ks][M][N] (W-row order), summed by the combine kernel
     const int nn = dg_row(p, t, nl);
-    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][mm];
+    if (mm < p.M && nn < p.N) p.ws[((long)ks * p.M + mm) * p.N + nn] = tile_s[nl][ml];
     return;
   }
   if (p.epi == VP_EPI_SWIGLU_IL || p.epi == VP_EPI_SWIGLU_HALVES) {
     if (threadIdx.x < 128 && mm < p.M) {
-      float v = tile_s[nl][mm], u = tile_s[nl + 8][mm];
+      float v = tile_s[nl][ml], u = tile_s[nl + 8][ml];
       if (ROWSCALE) { v *= p.wscale[dg_row(p, t, nl)]; u *= p.wscale[dg_row(p, t, nl + 8)]; }
       dg_store(p, mm, 8 * t + nl, v, u);
     }
     return;
   }
   if (mm < p.M && 16 * t + nl < p.N) {
-    float v = tile_s[nl][mm];
+    float v = tile_s[nl][ml];
     if (ROWSCALE) v *= p.wscale[16 * t + nl];
     dg_store(p, mm, 16 * t + nl, v, 0.f);
   }
@@ -545,6 +548,255 @@ __global__ __launch_bounds__(DG_THREADS, 4) void decode_gemm_w4_kernel(DecGemmAr
   }
 #undef DG4_STEP
   dg_reduce_store<false>(p, acc, t, ks, w, lane, red, tile_s);
+}
+
+// ---------------------------------------------------------------- wide decode GEMMs: 17 <= M <= 64 ---------------
+// Decode is weight-bound, so more sequences per step are nearly free as long as every weight byte is still streamed once: the wide kernels
+// keep the block of the kernels above (one 16-row W tile, K over the 4 waves and KS blocks, the same chunk, loads and conversion per
+// format) and serve MT = ceil(M / 16) 16-row A tiles from each converted W fragment, one f32x4 accumulator per tile.  Output column m is the
+// MFMA column of A row m alone: tile j, lane row r reads A row min(16 j + r, M - 1), the chunk order, the order inside a chunk, the 4-wave
+// reduction (dg_reduce_store per tile, in tile order) and the combine are those of the M <= 16 kernels, so every row equals, bit for bit,
+// what the M <= 16 entry point returns for it inside any 16-row slice of A.  The norm prologue stays in the block (dg_rstd_rows over all M
+// rows); gamma is loaded once per part and shared by the tiles.
+template <int MT>
+struct DgRows {
+  const bf16_t* ar[MT];                      // this lane's A row of every tile
+  float rs[MT];                              // its rstd (1 without the norm prologue)
+};
+
+template <bool NORM, int MT>
+__device__ __forceinline__ DgRows<MT> dg_wide_rows(const DecGemmArgs& p, int r, const float* rstd_s) {
+  DgRows<MT> a;
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+    const int m = min(16 * j + r, p.M - 1);  // rows past M are clamped to the last valid row: never stored
+    a.ar[j] = p.A + (long)m * p.lda;
+    a.rs[j] = NORM ? rstd_s[m] : 1.f;
+  }
+  return a;
+}
+
+// the tiles' reductions in tile order; between two of them a barrier: tile j - 1's tile_s reads are done before red / tile_s are rewritten
+template <bool ROWSCALE, int MT, int J = 0>
+__device__ __forceinline__ void dg_wide_reduce_store(const DecGemmArgs& p, const f32x4* acc, int t, int ks, int w, int lane,
+                                                     float (*red)[256], float (*tile_s)[17]) {
+  if constexpr (J < MT) {
+    if (J) __syncthreads();
+    dg_reduce_store<ROWSCALE, 16 * J>(p, acc[J], t, ks, w, lane, red, tile_s);
+    dg_wide_reduce_store<ROWSCALE, MT, J + 1>(p, acc, t, ks, w, lane, red, tile_s);
+  }
+}
+
+template <bool NORM, int MT>
+__global__ __launch_bounds__(DG_THREADS) void decode_gemm_wide_kernel(DecGemmArgs p) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16 * MT];
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const bf16_t* wr = p.W + (long)n * p.ldw;
+  const DgRows<MT> a = dg_wide_rows<NORM, MT>(p, r, rstd_s);
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  f32x4 acc[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c = kbeg + w * DG_KCHUNK; c < kend; c += 4 * DG_KCHUNK) {
+    const int k0 = c + g * 64;
+    const bool full = c + DG_KCHUNK <= kend;
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8 wv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (full) wv[u] = __builtin_nontemporal_load((const bf16x8*)(wr + k0 + u * 8));
+      else wv[u] = k0 + u * 8 < kend ? *(const bf16x8*)(wr + k0 + u * 8) : z;
+    }
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      bf16x8 av[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) av[u] = (full || k0 + u * 8 < kend) ? *(const bf16x8*)(a.ar[j] + k0 + u * 8) : z;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (NORM) {
+          if (full || k0 + u * 8 < kend) av[u] = dg_norm(av[u], p.gamma + k0 + u * 8, a.rs[j]);
+        }
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[u], av[u], acc[j], 0, 0, 0);
+      }
+    }
+  }
+  dg_wide_reduce_store<false, MT>(p, acc, t, ks, w, lane, red, tile_s);
+}
+
+// the A side of one part of a quantised chunk, shared by W8 and W4 (F fragments at the k offsets kk, already clamped).  Every tile's
+// A fragments (bf16, L2-resident; + gamma) are issued FIRST and the part's loads of the next chunk after them, as in dg8_chunk: the
+// memory counter retires in order, so waiting for A leaves those W loads in flight under the conversion
+template <bool NORM, int MT, int F>
+__device__ __forceinline__ void dg_wide_load_a(bf16x8 (*av)[F], bf16x8* gv, const int* kk, const DecGemmArgs& p, const DgRows<MT>& a) {
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+#pragma unroll
+    for (int u = 0; u < F; ++u) av[j][u] = *(const bf16x8*)(a.ar[j] + kk[u]);
+  }
+  if (NORM) {
+#pragma unroll
+    for (int u = 0; u < F; ++u) gv[u] = *(const bf16x8*)(p.gamma + kk[u]);
+  }
+}
+
+// ... and its MFMAs: the part's converted W fragments wf against every tile
+template <bool NORM, int MT, int F>
+__device__ __forceinline__ void dg_wide_mfma(f32x4* acc, const bf16x8* wf, bf16x8 (*av)[F], const bf16x8* gv, const DgRows<MT>& a) {
+#pragma unroll
+  for (int j = 0; j < MT; ++j) {
+#pragma unroll
+    for (int u = 0; u < F; ++u) {
+      if (NORM) av[j][u] = dg_norm(av[j][u], (const bf16_t*)&gv[u], a.rs[j]);
+      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[u], av[j][u], acc[j], 0, 0, 0);
+    }
+  }
+}
+
+// dg8_chunk for MT tiles, in parts of 2 loads (4 fragments): the MFMA order of a row is that of dg8_chunk (loads 0 .. 7, low half then high)
+template <bool NORM, int NEXT, int MT>
+__device__ __forceinline__ void dg8_wide_chunk(f32x4* acc, const u32x4* wq, u32x4* wn, const DecGemmArgs& p, const uint8_t* wr,
+                                               const DgRows<MT>& a, int k0, int kend, bool full) {
+  constexpr int L = 2;
+#pragma unroll
+  for (int h = 0; h < 8 / L; ++h) {
+    int kk[2 * L];
+#pragma unroll
+    for (int u = 0; u < 2 * L; ++u) {
+      const int k = k0 + (h * L + (u >> 1)) * 64 + (u & 1) * 8;    // the two halves of load h * L + u / 2
+      kk[u] = full ? k : min(k, kend - 8);
+    }
+    bf16x8 av[MT][2 * L], gv[2 * L], wf[2 * L];
+    dg_wide_load_a<NORM, MT, 2 * L>(av, gv, kk, p, a);
+    if (NEXT) dg8_load<L>(wn + L * h, wr, k0 + 4 * DG8_KCHUNK + h * L * 64, kend, NEXT == 1);
+    __builtin_amdgcn_sched_barrier(0);                           // the loads above stay above: no conversion is hoisted over them (registers)
+#pragma unroll
+    for (int u = 0; u < L; ++u) {
+      u32x4 wv = wq[h * L + u];
+      asm volatile("" : "+v"(wv));                                 // pins the conversion below the loads of its own part
+      dg8_cvt(wv, wf[2 * u], wf[2 * u + 1]);
+    }
+    dg_wide_mfma<NORM, MT, 2 * L>(acc, wf, av, gv, a);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <bool NORM, int MT>
+__global__ __launch_bounds__(DG_THREADS, 2) void decode_gemm_w8_wide_kernel(DecGemmArgs p) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16 * MT];
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const uint8_t* wr = (const uint8_t*)p.W + (long)n * p.ldw;
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  int c = kbeg + w * DG8_KCHUNK;
+  u32x4 w0[8], w1[8];                                            // ping-pong: one chunk converts while the next one streams
+  if (c < kend) dg8_load<8>(w0, wr, c + g * 16, kend, c + DG8_KCHUNK <= kend);       // the first chunk is in flight under the rstd pass
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
+  const DgRows<MT> a = dg_wide_rows<NORM, MT>(p, r, rstd_s);
+  f32x4 acc[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#define DG8_STEP(WQ, WN)                                                                                          \
+  {                                                                                                               \
+    const int cn = c + 4 * DG8_KCHUNK, k0 = c + g * 16;                                                           \
+    const bool full = c + DG8_KCHUNK <= kend;                                                                     \
+    if (cn >= kend) dg8_wide_chunk<NORM, 0, MT>(acc, WQ, WN, p, wr, a, k0, kend, full);                           \
+    else if (cn + DG8_KCHUNK <= kend) dg8_wide_chunk<NORM, 1, MT>(acc, WQ, WN, p, wr, a, k0, kend, full);         \
+    else dg8_wide_chunk<NORM, 2, MT>(acc, WQ, WN, p, wr, a, k0, kend, full);                                      \
+    c = cn;                                                                                                       \
+  }
+  while (c < kend) {                                             // c is wave-uniform: scalar branches
+    DG8_STEP(w0, w1)
+    if (c >= kend) break;
+    DG8_STEP(w1, w0)
+  }
+#undef DG8_STEP
+  dg_wide_reduce_store<true, MT>(p, acc, t, ks, w, lane, red, tile_s);
+}
+
+// dg4_chunk for MT tiles, in parts of 1 load (4 fragments)
+template <bool NORM, int NEXT, int MT>
+__device__ __forceinline__ void dg4_wide_chunk(f32x4* acc, const u32x4* wq, const u32x4 sq, int ssh, u32x4* wn, u32x4& sn,
+                                               const DecGemmArgs& p, const uint8_t* wr, const uint8_t* er, const DgRows<MT>& a, int c, int g,
+                                               int kend, bool full, bool evec) {
+  const int k0 = c + g * 32;
+#pragma unroll
+  for (int h = 0; h < DG4_LOADS; ++h) {
+    int kk[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const int k = k0 + h * 128 + f * 8;                          // the four quarters of load h
+      kk[f] = full ? k : min(k, kend - 8);
+    }
+    bf16x8 av[MT][4], gv[4], wf[4];
+    dg_wide_load_a<NORM, MT, 4>(av, gv, kk, p, a);
+    if (NEXT) {
+      if (h == 0) sn = dg4_load_scales(er, c + 4 * DG4_KCHUNK, g, kend, NEXT == 1 && evec);
+      dg4_load<1>(wn + h, wr, k0 + 4 * DG4_KCHUNK + h * 128, kend, NEXT == 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);                           // the loads above stay above: no conversion is hoisted over them (registers)
+    u32x4 wv = wq[h];
+    asm volatile("" : "+v"(wv));                                   // pins the conversion below the loads of its own part
+    // 2^(byte - 127) as fp32 bits: byte << 23 (byte >= 7: a normal number)
+    const float sc = __builtin_bit_cast(float, ((sq[h] >> ssh) & 0xffu) << 23);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) wf[f] = dg4_cvt(wv[f], sc);
+    dg_wide_mfma<NORM, MT, 4>(acc, wf, av, gv, a);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <bool NORM, int MT>
+__global__ __launch_bounds__(DG_THREADS, 2) void decode_gemm_w4_wide_kernel(DecGemmArgs p) {
+  __shared__ float red[4][256];
+  __shared__ float tile_s[16][17];
+  __shared__ float rstd_s[16 * MT];
+  const int t = blockIdx.x, ks = blockIdx.y;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int n = min(dg_row(p, t, r), p.N - 1);
+  const uint8_t* wr = (const uint8_t*)p.W + (long)n * p.ldw;
+  const uint8_t* er = p.E + (long)n * p.lde;
+  const int kbeg = ks * p.Kc, kend = kbeg + p.Kc;
+  const bool evec = ((((uintptr_t)p.E) | (uintptr_t)p.lde) & 15) == 0;
+  int c = kbeg + w * DG4_KCHUNK;
+  u32x4 w0[DG4_LOADS], w1[DG4_LOADS], s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};  // ping-pong: one chunk converts while the next one streams
+  if (c < kend) {                                                // the first chunk is in flight under the rstd pass
+    s0 = dg4_load_scales(er, c, g, kend, evec && c + DG4_KCHUNK <= kend);
+    dg4_load<DG4_LOADS>(w0, wr, c + g * 32, kend, c + DG4_KCHUNK <= kend);
+  }
+  if (NORM) dg_rstd_rows(p, w, lane, rstd_s);
+  const DgRows<MT> a = dg_wide_rows<NORM, MT>(p, r, rstd_s);
+  f32x4 acc[MT];
+#pragma unroll
+  for (int j = 0; j < MT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#define DG4_STEP(WQ, SQ, WN, SN)                                                                                           \
+  {                                                                                                                        \
+    const int cn = c + 4 * DG4_KCHUNK;                                                                                     \
+    const bool full = c + DG4_KCHUNK <= kend;                                                                              \
+    const int ssh = (full && evec) ? 8 * g : 0;                                                                            \
+    if (cn >= kend) dg4_wide_chunk<NORM, 0, MT>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, a, c, g, kend, full, evec);           \
+    else if (cn + DG4_KCHUNK <= kend) dg4_wide_chunk<NORM, 1, MT>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, a, c, g, kend, full, evec); \
+    else dg4_wide_chunk<NORM, 2, MT>(acc, WQ, SQ, ssh, WN, SN, p, wr, er, a, c, g, kend, full, evec);                      \
+    c = cn;                                                                                                                \
+  }
+  while (c < kend) {                                             // c is wave-uniform: scalar branches
+    DG4_STEP(w0, s0, w1, s1)
+    if (c >= kend) break;
+    DG4_STEP(w1, s1, w0, s0)
+  }
+#undef DG4_STEP
+  dg_wide_reduce_store<false, MT>(p, acc, t, ks, w, lane, red, tile_s);
 }
 
 // ---------------------------------------------------------------- RoPE + KV append ---------------
@@ -1018,6 +1270,7 @@ __global__ __launch_bounds__(256) void decode_attn_split_kv8_kernel(const bf16_t
 // What differs between the three GEMM entry points: their wording, the format's divisibility rules, its chunk and its kernels
 struct DgFormat {
   const char* name;                          // the entry point, for the messages
+  const char* wide_name;                     // its wide (M <= 64) entry point
   const char* operands;                      // the pointers that must not be null, as the message lists them
   const char* m_hint;                        // closes the M range of the message
   const char* rule;                          // the shape rule, as the message states it
@@ -1025,14 +1278,20 @@ struct DgFormat {
   int kmul, ldwmul, kper;                    // K, ldw must be multiples of kmul, ldwmul; ldw >= K / kper
   bool rowscale, blocks;                     // needs w_scale | E and lde >= K / 32
   void (*kernel[2])(DecGemmArgs);            // without | with the norm prologue
+  void (*wide[2][3])(DecGemmArgs);           // 17 <= M <= 64: the same for 2 | 3 | 4 A tiles of 16 rows
 };
-static const DgFormat DG_BF16 = {"vp_decode_gemm", "A / W / C", "; larger M: vp_gemm_bf16", "K, lda, ldw multiples of 8, lda / ldw >= K",
-                                 DG_KCHUNK, 8, 8, 1, false, false, {decode_gemm_kernel<false>, decode_gemm_kernel<true>}};
-static const DgFormat DG_W8 = {"vp_decode_gemm_w8", "A / W / w_scale / C", "", "K, ldw multiples of 16, lda of 8, lda / ldw >= K",
-                               DG8_KCHUNK, 16, 16, 1, true, false, {decode_gemm_w8_kernel<false>, decode_gemm_w8_kernel<true>}};
-static const DgFormat DG_W4 = {"vp_decode_gemm_w4", "A / W / E (block scales) / C", "",
-                               "K a multiple of 32, ldw (bytes) of 16, lda of 8, lda >= K, ldw >= K / 2, lde >= K / 32",
-                               DG4_KCHUNK, 32, 16, 2, false, true, {decode_gemm_w4_kernel<false>, decode_gemm_w4_kernel<true>}};
+#define DG_WIDE(K) {{K<false, 2>, K<false, 3>, K<false, 4>}, {K<true, 2>, K<true, 3>, K<true, 4>}}
+static const DgFormat DG_BF16 = {"vp_decode_gemm", "vp_decode_gemm_wide", "A / W / C", "; 17 <= M <= 64: vp_decode_gemm_wide; larger M: vp_gemm_bf16",
+                                 "K, lda, ldw multiples of 8, lda / ldw >= K", DG_KCHUNK, 8, 8, 1, false, false,
+                                 {decode_gemm_kernel<false>, decode_gemm_kernel<true>}, DG_WIDE(decode_gemm_wide_kernel)};
+static const DgFormat DG_W8 = {"vp_decode_gemm_w8", "vp_decode_gemm_w8_wide", "A / W / w_scale / C", "; 17 <= M <= 64: vp_decode_gemm_w8_wide",
+                               "K, ldw multiples of 16, lda of 8, lda / ldw >= K", DG8_KCHUNK, 16, 16, 1, true, false,
+                               {decode_gemm_w8_kernel<false>, decode_gemm_w8_kernel<true>}, DG_WIDE(decode_gemm_w8_wide_kernel)};
+static const DgFormat DG_W4 = {"vp_decode_gemm_w4", "vp_decode_gemm_w4_wide", "A / W / E (block scales) / C",
+                               "; 17 <= M <= 64: vp_decode_gemm_w4_wide",
+                               "K a multiple of 32, ldw (bytes) of 16, lda of 8, lda >= K, ldw >= K / 2, lde >= K / 32", DG4_KCHUNK, 32, 16, 2,
+                               false, true, {decode_gemm_w4_kernel<false>, decode_gemm_w4_kernel<true>}, DG_WIDE(decode_gemm_w4_wide_kernel)};
+#undef DG_WIDE
 
 static long dg_workspace_bytes(int M, int N, int K, int epilogue, int kchunk) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
@@ -1040,37 +1299,41 @@ static long dg_workspace_bytes(int M, int N, int K, int epilogue, int kchunk) {
   return ks > 1 ? (long)ks * M * N * (long)sizeof(float) : 0;
 }
 
-// the three GEMM entry points: checks, the main kernel and, where K is split, the combine
-static int dg_run(const DgFormat& f, int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale,
+// the three GEMM entry points and their wide forms (M <= 64; at M <= 16 they launch the same kernel as their parents): checks, the main
+// kernel and, where K is split, the combine
+static int dg_run(const DgFormat& f, bool wide, int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale,
                   const void* E, long lde, void* C, long ldc, const void* residual, long ldr, const void* norm_w, float eps, int epilogue,
                   int out_f32, float* workspace, hipStream_t stream) {
-  VP_REQUIRE(A && W && C && (!f.rowscale || w_scale) && (!f.blocks || E), VP_ERR_BAD_ARG, "%s: null %s", f.name, f.operands);
-  VP_REQUIRE(M >= 1 && M <= 16, VP_ERR_UNSUPPORTED_SHAPE, "%s: M = %d (1 <= M <= 16%s)", f.name, M, f.m_hint);
+  const char* name = wide ? f.wide_name : f.name;
+  VP_REQUIRE(A && W && C && (!f.rowscale || w_scale) && (!f.blocks || E), VP_ERR_BAD_ARG, "%s: null %s", name, f.operands);
+  VP_REQUIRE(M >= 1 && M <= (wide ? 64 : 16), VP_ERR_UNSUPPORTED_SHAPE, "%s: M = %d (1 <= M <= %d%s)", name, M, wide ? 64 : 16,
+             wide ? "" : f.m_hint);
   char lde_s[40] = "";
   if (f.blocks) snprintf(lde_s, sizeof(lde_s), ", lde = %ld", lde);
   VP_REQUIRE(N > 0 && K > 0 && K % f.kmul == 0 && lda % 8 == 0 && ldw % f.ldwmul == 0 && lda >= K && ldw >= K / f.kper &&
-             (!f.blocks || lde >= K / 32), VP_ERR_UNSUPPORTED_SHAPE, "%s: N = %d, K = %d, lda = %ld, ldw = %ld%s (%s)", f.name, N, K, lda,
+             (!f.blocks || lde >= K / 32), VP_ERR_UNSUPPORTED_SHAPE, "%s: N = %d, K = %d, lda = %ld, ldw = %ld%s (%s)", name, N, K, lda,
              ldw, lde_s, f.rule);
   VP_REQUIRE(((((uintptr_t)A) | ((uintptr_t)W) | (uintptr_t)(norm_w ? norm_w : A)) & 15) == 0, VP_ERR_UNSUPPORTED_SHAPE,
-             "%s: A, W and norm_w must be 16-byte aligned", f.name);
+             "%s: A, W and norm_w must be 16-byte aligned", name);
   const bool swiglu = epilogue == VP_EPI_SWIGLU_IL || epilogue == VP_EPI_SWIGLU_HALVES;
-  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "%s: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)", f.name,
+  VP_REQUIRE(epilogue == VP_EPI_NONE || swiglu, VP_ERR_BAD_ARG, "%s: epilogue %d (0 none | 4 SwiGLU interleaved | 5 SwiGLU halves)", name,
              epilogue);
   VP_REQUIRE(!swiglu || (N % 16 == 0 && !out_f32 && !residual), VP_ERR_UNSUPPORTED_SHAPE,
-             "%s: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", f.name, N);
-  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "%s: residual epilogue writes bf16 only", f.name);
-  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "%s: ldc / ldr too small", f.name);
+             "%s: SwiGLU needs N %% 16 == 0, bf16 output and no residual (N = %d)", name, N);
+  VP_REQUIRE(!(out_f32 && residual), VP_ERR_BAD_ARG, "%s: residual epilogue writes bf16 only", name);
+  VP_REQUIRE(ldc >= (swiglu ? N / 2 : N) && (!residual || ldr >= N), VP_ERR_BAD_ARG, "%s: ldc / ldr too small", name);
   const int ks = dg_ksplit(N, K, epilogue, f.kchunk);
   VP_REQUIRE(ks == 1 || workspace, VP_ERR_BAD_ARG, "%s: this shape splits K %d ways and needs %s_workspace_bytes() of workspace (got NULL)",
-             f.name, ks, f.name);
+             name, ks, name);
   const DecGemmArgs p{(const bf16_t*)A, (const bf16_t*)W, C, (const bf16_t*)residual, (const bf16_t*)norm_w, workspace,
                       M, N, K, K / ks, epilogue, out_f32 ? 1 : 0, ks, lda, ldw, ldc, ldr, eps, w_scale, (const uint8_t*)E, lde};
-  hipLaunchKernelGGL(f.kernel[norm_w != nullptr], dim3(swiglu ? N / 16 : (N + 15) / 16, ks), dim3(DG_THREADS), 0, stream, p);
+  const auto kernel = M <= 16 ? f.kernel[norm_w != nullptr] : f.wide[norm_w != nullptr][(M - 17) / 16];
+  hipLaunchKernelGGL(kernel, dim3(swiglu ? N / 16 : (N + 15) / 16, ks), dim3(DG_THREADS), 0, stream, p);
   if (ks > 1) {
     const long nout = (long)M * (swiglu ? N / 2 : N);
     hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, p);
   }
-  return vp_check_launch(f.name);
+  return vp_check_launch(name);
 }
 
 // the two attention entry points: everything but the format's own stride / alignment rule
@@ -1196,7 +1459,15 @@ long vp_decode_gemm_workspace_bytes(int M, int N, int K, int epilogue) { return 
 
 int vp_decode_gemm(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual,
                    long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, hipStream_t stream) {
-  return dg_run(DG_BF16, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+  return dg_run(DG_BF16, false, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+}
+
+// the wide forms (1 <= M <= 64) need the slabs alone: the norm prologue stays in the kernel, there is no pre-pass scratch
+long vp_decode_gemm_wide_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG_KCHUNK); }
+
+int vp_decode_gemm_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* residual,
+                        long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace, hipStream_t stream) {
+  return dg_run(DG_BF16, true, M, N, K, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_quant_rows_e4m3(int N, int K, void* W, long ldw, void* Q, long ldq, float* scale, int writeback, hipStream_t stream) {
@@ -1215,7 +1486,15 @@ long vp_decode_gemm_w8_workspace_bytes(int M, int N, int K, int epilogue) { retu
 int vp_decode_gemm_w8(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       hipStream_t stream) {
-  return dg_run(DG_W8, M, N, K, A, lda, W, ldw, w_scale, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+  return dg_run(DG_W8, false, M, N, K, A, lda, W, ldw, w_scale, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+}
+
+long vp_decode_gemm_w8_wide_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG8_KCHUNK); }
+
+int vp_decode_gemm_w8_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* w_scale, void* C, long ldc,
+                           const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
+                           hipStream_t stream) {
+  return dg_run(DG_W8, true, M, N, K, A, lda, W, ldw, w_scale, nullptr, 0, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_quant_blocks_mxfp4(int N, int K, void* W, long ldw, void* Q, long ldq, void* E, long lde, int writeback, hipStream_t stream) {
@@ -1235,7 +1514,15 @@ long vp_decode_gemm_w4_workspace_bytes(int M, int N, int K, int epilogue) { retu
 int vp_decode_gemm_w4(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C, long ldc,
                       const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32, float* workspace,
                       hipStream_t stream) {
-  return dg_run(DG_W4, M, N, K, A, lda, W, ldw, nullptr, E, lde, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+  return dg_run(DG_W4, false, M, N, K, A, lda, W, ldw, nullptr, E, lde, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
+}
+
+long vp_decode_gemm_w4_wide_workspace_bytes(int M, int N, int K, int epilogue) { return dg_workspace_bytes(M, N, K, epilogue, DG4_KCHUNK); }
+
+int vp_decode_gemm_w4_wide(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const void* E, long lde, void* C,
+                           long ldc, const void* residual, long ldr, const void* norm_w, float eps, int epilogue, int out_f32,
+                           float* workspace, hipStream_t stream) {
+  return dg_run(DG_W4, true, M, N, K, A, lda, W, ldw, nullptr, E, lde, C, ldc, residual, ldr, norm_w, eps, epilogue, out_f32, workspace, stream);
 }
 
 int vp_decode_rope_append(int B, int Hq, int Hkv, int D, const void* qkv, long ldqkv, void* q_out, long ldq, void* k_cache, long k_bs,

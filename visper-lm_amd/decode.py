@@ -7,6 +7,9 @@ IFT classes — the multimodal splice, then HF's generation loop over `inputs_em
   step      per layer: QKV (RMSNorm prologue) -> RoPE + KV append at pos[b] -> decode attention -> wo + residual -> gate_up (RMSNorm
             prologue, SwiGLU epilogue) -> down + residual; final norm folded into the fp32 lm_head launch; pos / kv_len += 1 on the device
 
+A step takes up to 64 sequences: up to 16 its GEMMs are the skinny entry points, above that the wide ones (vp_decode_gemm*_wide: one streamed
+weight for up to four 16-row tiles of rows, the same bits row for row; DecodeSession.wide_gemm = False runs the skinny ones per 16-row slice).
+
 Every per-token scalar (token ids, positions, cache lengths) lives on the device, so one step can be captured once into a CUDA graph
 (single stream, no fork) and replayed for every token (VP_DECODE_GRAPH=1; the default is eager launches: capture did not pay, see below).  Decode reads the same kernel-ready weights
 _decoder_fwd reads (fused qkv, gate|up in the engine's layout, folded gamma when fold_norm is on), so IFT-trained weights are current.
@@ -99,6 +102,14 @@ class KVCache:
 
 
 MAX_VERIFY_ROWS = 16                                             # the skinny GEMMs' M
+MAX_BATCH = ops.DECODE_GEMM_WIDE_ROWS                            # the wide GEMMs' M: sequences of one decode step
+
+
+def check_batch(B):
+    """Host-only, before any GPU work: a step's GEMMs have one row per sequence and take at most MAX_BATCH."""
+    if int(B) > MAX_BATCH:
+        raise ValueError(f"generate: batch of {int(B)} sequences, a decode step takes at most {MAX_BATCH} (its GEMMs, vp_decode_gemm*_wide, "
+                         f"have 1 <= M <= {MAX_BATCH} rows); generate in groups of at most {MAX_BATCH} prompts")
 
 
 def check_lookup(B, n, do_sample=False, max_ngram=2):
@@ -174,7 +185,12 @@ def text_plan(eng, input_ids, attention_mask):
 class DecodeSession:
     """One generate() call: the cache, the preallocated step buffers and (optionally) the captured step.
     lookup = n > 0: verify mode (prompt-lookup decoding).  A step then runs R = B (n + 1) rows, row b (n + 1) + i at position pos_b + i on
-    cache row b, through verify() instead of step(); `steps` and `accepted` count the verify steps and the drafts they accepted."""
+    cache row b, through verify() instead of step(); `steps` and `accepted` count the verify steps and the drafts they accepted.
+    wide_gemm: how the GEMMs of a step with 17 .. 64 rows run (ops.decode_gemm's `wide`): None = the wide entry points, one call each;
+    False = the skinny entry points once per 16-row slice (the same tokens and logits: the verification and benchmark leg).  Set it before
+    prefill(); sessions of at most 16 rows do not read it."""
+
+    wide_gemm = None
 
     def __init__(self, eng, kv_cache_dtype=None, lookup=None):
         self.eng = eng
@@ -229,7 +245,7 @@ class DecodeSession:
         last = torch.from_numpy((np.arange(B) * S + lens - 1).astype(np.int32)).to(eng.dev)
         h_last = torch.empty(B, H, device=eng.dev, dtype=BF16)
         ops.gather_rows([dec["hidden"]], torch.zeros(B, device=eng.dev, dtype=I32), last, H, h_last)
-        logits = ops.decode_gemm(h_last, eng.fz["lm_head"], out_f32=True)
+        logits = ops.decode_gemm(h_last, eng.fz["lm_head"], out_f32=True, wide=self.wide_gemm)
         c.lens.copy_(torch.from_numpy(np.concatenate([lens, lens + 1]).astype(np.int32)))
         c.lens_host[:] = lens
         self._alloc(B)
@@ -252,7 +268,7 @@ class DecodeSession:
         self.epi = ops.EPI_SWIGLU_IL if eng.gu_interleaved else ops.EPI_SWIGLU_HALVES
         shapes = [(nqkv, H, 0), (H, nh * hd, 0), (2 * I, H, self.epi), (H, I, 0), (V, H, 0)]
         w4 = self.fq_format == "mxfp4"                           # the kernels the step can call: bf16 (lm_head may stay bf16) and the format's own
-        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep, w8=q and not w4, w4=q and w4) for N, K, ep in shapes
+        nb = max(ops.decode_gemm_ws_bytes(B, N, K, ep, w8=q and not w4, w4=q and w4, wide=self.wide_gemm) for N, K, ep in shapes
                  for q in ((False, True) if self.fq else (False,)))
         self.gws = e(max(1, nb // 4), dt=torch.float32) if nb > 0 else None
         Smax = self.cache.Smax
@@ -276,6 +292,7 @@ class DecodeSession:
     def _gemm(self, a, key, **kw):
         """One skinny GEMM of the step on weight `key`: its quantised copy when the session decodes from one, else the bf16 weight."""
         q = self.fq.get(key) if self.fq else None
+        kw["wide"] = self.wide_gemm
         if q is None:
             return ops.decode_gemm(a, self.eng.fz[key], **kw)
         if self.fq_format == "mxfp4":
@@ -407,13 +424,14 @@ def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None,
              top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False,
              kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, drafter=None):
     """Greedy / sampled decoding of B prompts, each continuing at its own length -> LongTensor [B, n_new] of the new tokens only (rows that
-    finished are padded with pad_token_id after their EOS).  return_logits: also the fp32 logits [B, V] each token was chosen from.
+    finished are padded with pad_token_id after their EOS); B <= 64 (check_batch).  return_logits: also the fp32 logits [B, V] each token was chosen from.
     kv_cache_dtype: None (the engine's default, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" (KVCache).
     prompt_lookup_num_tokens = n > 0 (HF's argument; greedy only, B (n + 1) <= 16): prompt-lookup decoding with n drafts per step from
     lookup_draft(history, n, max_matching_ngram_size), or from drafter(b, history) -> list of ids (no HF argument: the test and benchmark
     hook).  The result, the streamer calls and the logits are those of the plain path."""
     B = input_ids.shape[0]
     lookup = check_lookup(B, prompt_lookup_num_tokens, do_sample, max_matching_ngram_size)
+    check_batch(B)
     if lookup:
         return _generate_lookup(eng, input_ids, attention_mask, images, group_sizes, int(max_new_tokens), eos_token_id, pad_token_id, streamer,
                                 use_graph, return_logits, kv_cache_dtype, lookup, int(max_matching_ngram_size), drafter)

@@ -151,6 +151,7 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
     max_ngram = kwargs.pop("max_matching_ngram_size", None)
     max_ngram = 2 if max_ngram is None else int(max_ngram)
     lookup = decode.check_lookup(inputs.shape[0], lookup, do_sample, max_ngram)
+    decode.check_batch(inputs.shape[0])                              # more sequences than a decode step takes: refused before the engine is built
     with torch.no_grad():
         module._sync_trainable()
         eng = module._get_engine()

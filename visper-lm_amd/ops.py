@@ -658,15 +658,34 @@ def adamw_(p, g, m, v, shadow, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
 EPI_SWIGLU_IL, EPI_SWIGLU_HALVES = 4, 5
 
 
-def decode_gemm_ws_bytes(M, N, K, epi=EPI_NONE, w8=False, w4=False):
+DECODE_GEMM_ROWS = 16                                            # rows of one vp_decode_gemm* call (one 16-row A tile)
+DECODE_GEMM_WIDE_ROWS = 64                                       # ... of one vp_decode_gemm*_wide call (up to four)
+
+
+def _decode_gemm_route(M, wide):
+    """(entry point suffix, rows per call) of an M-row decode GEMM.  M <= 16: the skinny entry point.  17 .. 64: the wide one in one call
+    (wide None / True) or, wide=False, the skinny one once per 16-row slice: the same bits (output row m depends on A row m alone), kept as
+    the verification and benchmark leg."""
+    if M > DECODE_GEMM_WIDE_ROWS:
+        raise ValueError(f"decode_gemm: M = {M} rows, the decode GEMMs take at most {DECODE_GEMM_WIDE_ROWS} (larger M: gemm_nt)")
+    if M <= DECODE_GEMM_ROWS or wide is False:
+        return "", DECODE_GEMM_ROWS
+    return "_wide", DECODE_GEMM_WIDE_ROWS
+
+
+def decode_gemm_ws_bytes(M, N, K, epi=EPI_NONE, w8=False, w4=False, wide=None):
     assert not (w8 and w4)
-    name = "vp_decode_gemm_w4_workspace_bytes" if w4 else ("vp_decode_gemm_w8_workspace_bytes" if w8 else "vp_decode_gemm_workspace_bytes")
-    return int(_lib.raw(name, M, N, K, epi))
+    suffix, rows = _decode_gemm_route(M, wide)
+    name = "vp_decode_gemm" + ("_w4" if w4 else "_w8" if w8 else "") + suffix + "_workspace_bytes"
+    return int(_lib.raw(name, min(M, rows), N, K, epi))
 
 
-def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f32=False, out=None, ws=None, w_scale=None, w_block_scale=None):
-    """out[M, N] = epi(norm(a)[M, K] @ w[N, K]^T) for M <= 16 (vp_decode_gemm): weight-streaming, optional RMSNorm prologue (gamma norm_w),
+def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f32=False, out=None, ws=None, w_scale=None, w_block_scale=None,
+                wide=None):
+    """out[M, N] = epi(norm(a)[M, K] @ w[N, K]^T) for M <= 64: weight-streaming, optional RMSNorm prologue (gamma norm_w),
     + residual, SwiGLU on the fused gate|up weight (epi EPI_SWIGLU_IL / EPI_SWIGLU_HALVES: out [M, N/2]), fp32 output (logits).
+    M <= 16: vp_decode_gemm.  17 <= M <= 64: vp_decode_gemm_wide in one call, which streams w once; wide=False: vp_decode_gemm once per
+    16-row slice of a / residual / out (the same bits).  M > 64: ValueError.
     ws: caller-owned fp32 workspace of at least decode_gemm_ws_bytes() (allocated here when None).
     w_scale (fp32 [N]): w is uint8 [N, K] of e4m3fn bytes with one power-of-two scale per row (quant_rows_e4m3) -> vp_decode_gemm_w8.
     w_block_scale (uint8 [N, K/32]): w is uint8 [N, K/2] of packed e2m1 codes with one e8m0 scale byte per block of 32 k
@@ -689,17 +708,22 @@ def decode_gemm(a, w, residual=None, norm_w=None, eps=1e-5, epi=EPI_NONE, out_f3
         out = torch.empty(M, nout, device=a.device, dtype=torch.float32 if out_f32 else BF16)
     _, _, ldc = _rows2d(out)
     ldr = 0 if residual is None else _rows2d(residual)[2]
+    suffix, rows = _decode_gemm_route(M, wide)
     if ws is None:
-        nb = decode_gemm_ws_bytes(M, N, K, epi, w8, w4)
+        nb = decode_gemm_ws_bytes(M, N, K, epi, w8, w4, wide)
         ws = torch.empty(max(1, nb // 4), device=a.device, dtype=torch.float32) if nb > 0 else None
-    head = (M, N, K, _p(a), lda, _p(w), ldw)
-    tail = (_p(out), ldc, _p(residual), ldr, _p(norm_w), float(eps), int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
-    if w8:
-        _lib.call("vp_decode_gemm_w8", *head, _p(w_scale), *tail)
-    elif w4:
-        _lib.call("vp_decode_gemm_w4", *head, _p(w_block_scale), w_block_scale.stride(0), *tail)
-    else:
-        _lib.call("vp_decode_gemm", *head, *tail)
+    # one call, or the skinny entry point on every 16-row slice
+    parts = [(a, out, residual)] if M <= rows else [(a[m:m + rows], out[m:m + rows], None if residual is None else residual[m:m + rows])
+                                                    for m in range(0, M, rows)]
+    for ac, oc, rc in parts:
+        head = (ac.shape[0], N, K, _p(ac), lda, _p(w), ldw)
+        tail = (_p(oc), ldc, _p(rc), ldr, _p(norm_w), float(eps), int(epi), 1 if out.dtype == torch.float32 else 0, _p(ws), _stream())
+        if w8:
+            _lib.call("vp_decode_gemm_w8" + suffix, *head, _p(w_scale), *tail)
+        elif w4:
+            _lib.call("vp_decode_gemm_w4" + suffix, *head, _p(w_block_scale), w_block_scale.stride(0), *tail)
+        else:
+            _lib.call("vp_decode_gemm" + suffix, *head, *tail)
     return out
 
 
