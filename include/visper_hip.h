@@ -353,6 +353,31 @@ int vp_decode_attn_kv8_rows(int B, int Hq, int Hkv, int D, int Smax, const void*
  * 1 <= i <= j; base_pos[b] += n_acc[b] + 1; pos[b, i] = base_pos[b] + i and kv_len[b, i] = pos[b, i] + 1 for the next step's rows;
  * tok[b, 0] = next[b, n_acc[b]].  n = 0 is the one-token step's + 1.  No workspace.  Null pointers, B <= 0 or n < 0: VP_ERR_BAD_ARG. */
 int vp_decode_accept(int B, int n, const int* next, int* tok, int* base_pos, int* pos, int* kv_len, int* n_acc, vp_stream_t stream);
+/* Token selection on the device: HF's RepetitionPenaltyLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper, then
+ * greedy or sampling, for R rows of RAW fp32 logits [R, V] (row stride ld_logits >= V; never modified), 1 <= V <= 2^20.  Per row, in fp32 IEEE
+ * arithmetic (correctly rounded divisions: the scores are reproducible bit for bit on a CPU):
+ *   1. penalty      x = seen[v] ? (l < 0 ? l * repetition_penalty : l / repetition_penalty) : l          (repetition_penalty 1 = off)
+ *   2. temperature  s = x / temperature
+ *   3. top-k        k = min(max(top_k, 1), V): every s >= the k-th largest value is kept, ties included      (top_k 0 = off)
+ *   4. top-p        over the survivors, p ~ exp(s - max): v is kept iff the mass of the survivors u with s_u <= s_v exceeds 1 - top_p; the
+ *                   largest is always kept                                                                 (top_p 1 = off)
+ *   5. scores_out   (fp32 [R, V], stride ld_scores >= V, NULL = off) = s where kept, -inf where removed: what HF's chain returns
+ *   6. greedy       (do_sample 0) the smallest index of the largest s
+ *   7. sampling     the kept tokens in ascending index order; the token whose interval of the cumulative distribution of p contains u
+ *                   (fp32 in [0, 1)): torch.multinomial's distribution on a different random stream.  Masses are exp(s - max) * 2^40 as
+ *                   integers, so sums are exact in any order: tokens and scores_out are the same from run to run.
+ * seen: uint32 [R, ceil(V / 32)], caller-owned, zeroed once by the caller: bit v of row r = the row was given token v before; the bit of the
+ *   selected token is set (NULL allowed when repetition_penalty is 1).  u: fp32 [u_steps, R], row min(*col, u_steps - 1) is read (u_steps 1:
+ *   a plain [R]); NULL allowed when do_sample is 0.  eos: int32 [n_eos] on the device, 0 <= n_eos <= 64.  col: ONE int32 on the device, the
+ *   output column (read on the device so that a captured step replays; the caller advances it, vp_add_i32).
+ * Writes tok[r] = the selected token (always the raw choice: the next step's input); out[r, *col] (int32 [R, n_out], stride ld_out; nothing
+ *   when *col is outside [0, n_out)) = pad if finished[r] was set, else the token; finished[r] |= (that output is in eos).
+ * For any input bits (NaN rows included) the kernel ends and tok[r] lies in [0, V).  No workspace.  Null required pointers and scalars
+ * outside their ranges: VP_ERR_BAD_ARG before any launch. */
+int vp_decode_select(int R, int V, const float* logits, long ld_logits, int do_sample, float temperature, int top_k, float top_p,
+                     float repetition_penalty, unsigned int* seen, const float* u, int u_steps, const int* eos, int n_eos, int pad,
+                     int* finished, const int* col, int* tok, int* out, long ld_out, int n_out, float* scores_out, long ld_scores,
+                     vp_stream_t stream);
 /* x[i] += delta for n int32 on the device (the per-sequence position / length counters of a decode step, advanced without a host round trip) */
 int vp_add_i32(long n, int* x, int delta, vp_stream_t stream);
 

@@ -45,6 +45,20 @@ quarter until it does, and every run records the text_tokens it used.  A cell is
 fastest chunked run.  Default --out: profiles/decode_bench_{llama3,phi3}_wide.json, which collects the cells of every --weights run.
 
   python tools/decode_bench.py --model llama3 --wide --weights mxfp4
+
+--select: token selection between two steps, torch against the device selector (vp_decode_select).  Per batch size (default 1,8,64) and
+for eager launches and the captured step, three legs alternate, --repeats runs each, in one process on the same engine and prompts:
+  torch        what generate() does per token without the new arguments: step, decode.next_tokens(do_sample, temperature 0.8, top_p 0.9:
+               sort, softmax, cumsum, scatter, multinomial), the EOS / pad bookkeeping and its host read of `finished` every token
+  device       the same sampling configuration selected on the device at the end of the step, `finished` read every token (sync_every 1)
+  device_k50   the device leg with top_k 50 and repetition_penalty 1.1 on top, `finished` read every 16 tokens (no torch counterpart)
+Sampling with temperature 0.8, top_p 0.9 is the one sampled configuration both paths can run.  The EOS id is one that stops nothing, so
+every leg decodes --new tokens.  A cell is a "gain" only if the slowest device run lies below the fastest torch run (and a "loss" the other
+way round); device_k50 is reported beside them.  The logits are a random-init model's: nearly flat, so top_p 0.9 keeps most of the
+vocabulary, which is the selector's most expensive case.  Where a batch does not fit, the text is shortened by a quarter until it does.
+Default --out: profiles/decode_bench_{llama3,phi3}_select.json.
+
+  python tools/decode_bench.py --model llama3 --select
 """
 import argparse
 import json
@@ -212,6 +226,99 @@ def wide_legs(eng, weights, B, new, text_tokens, repeats, use_graph):
                 verdict=("same kernel" if B <= 16 else "gain" if gain else "no gain"), runs=legs["wide"] + legs["chunked"])
 
 
+SELECT_LEGS = {"torch": None, "device": dict(sync_every=1), "device_k50": dict(top_k=50, repetition_penalty=1.1, sync_every=16)}
+
+
+def time_select(eng, B, new, text_tokens, use_graph, leg):
+    """One run of one --select leg: generate()'s per-token work of that path (decode.generate / decode._generate_device), the loop's early
+    exit left out, timed over new - 1 tokens after one warm-up / capture step"""
+    from visper_lm_amd import decode
+    ids, images = prompt(eng, B, text_tokens)
+    sess = decode.DecodeSession(eng)
+    sess.use_graph = use_graph
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    V = eng.fz["lm_head"].shape[0]
+    eos, pad = [V - 1], 0
+    dev = SELECT_LEGS[leg]
+    torch.cuda.synchronize()
+    logits = sess.prefill(ids, None, images, None, new + 1)
+    enq, reads = [], 0
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    if dev is None:
+        eos_t = torch.tensor(eos, device="cuda", dtype=torch.long)
+        finished = torch.zeros(B, device="cuda", dtype=torch.bool)
+
+        def choose(logits, finished):                             # decode.generate's loop body after the step
+            raw = decode.next_tokens(logits, True, 0.8, 0.9, gen).to(torch.long)
+            nxt = torch.where(finished, torch.full_like(raw, pad), raw)
+            finished = finished | torch.isin(nxt, eos_t)
+            bool(finished.all())
+            return raw, finished
+
+        tok, finished = choose(logits, finished)
+        tok, finished = choose(sess.step(tok), finished)           # first step: capture (graph) / warm-up (eager), not timed
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(new - 1):
+            h0 = time.perf_counter()
+            logits = sess.step(tok)
+            tok, finished = choose(logits, finished)
+            enq.append((time.perf_counter() - h0) * 1e3)
+            reads += 1
+        e1.record()
+    else:
+        sess.alloc_select(B, new + 1, eos, pad, True, 0.8, dev.get("top_k", 0), 0.9, dev.get("repetition_penalty", 1.0), gen)
+        sess.select_first(logits)
+        sess.step_select()
+        torch.cuda.synchronize()
+        e0.record()
+        for i in range(new - 1):
+            h0 = time.perf_counter()
+            sess.step_select()
+            if (i + 1) % dev["sync_every"] == 0 or i == new - 2:
+                bool((sess.finished != 0).all())
+                reads += 1
+            enq.append((time.perf_counter() - h0) * 1e3)
+        e1.record()
+    torch.cuda.synchronize()
+    enq.sort()
+    return dict(B=B, leg=leg, graph=use_graph, text_tokens=text_tokens, prompt_rows=int(sess.cache.lens_host.max()) - new,
+                ms_per_token=round(e0.elapsed_time(e1) / (new - 1), 4), host_ms_per_token_median=round(enq[len(enq) // 2], 4),
+                host_reads=reads, tokens_timed=new - 1)
+
+
+def select_legs(eng, B, new, text_tokens, repeats, use_graph, on_run=None):
+    """the three --select legs alternately on one engine -> dict with the medians and the verdict of device against torch; on_run(r) gets
+    every run as soon as it is done (the output file is rewritten with every run)"""
+    legs = {k: [] for k in SELECT_LEGS}
+    for _ in range(repeats):
+        for leg in legs:
+            while True:
+                try:
+                    r = time_select(eng, B, new, text_tokens, use_graph, leg)
+                    break
+                except torch.cuda.OutOfMemoryError:
+                    torch.cuda.empty_cache()
+                    text_tokens = text_tokens * 3 // 4
+                    if text_tokens < 16:
+                        raise
+            legs[leg].append(r)
+            print(json.dumps(r), flush=True)
+            if on_run is not None:
+                on_run(r)
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    t = {k: [r["ms_per_token"] for r in v] for k, v in legs.items()}
+    texts = sorted({r["text_tokens"] for v in legs.values() for r in v})
+    verdict = "gain" if max(t["device"]) < min(t["torch"]) else "loss" if min(t["device"]) > max(t["torch"]) else "no difference"
+    cell = dict(B=B, graph=use_graph, repeats=repeats, prompt=f"1 image + {texts[0]} text tokens", same_prompt_in_every_run=len(texts) == 1,
+                sampling="do_sample, temperature 0.8, top_p 0.9", verdict_device_vs_torch=verdict,
+                device_over_torch=round(med(t["device"]) / med(t["torch"]), 4), device_k50_over_torch=round(med(t["device_k50"]) / med(t["torch"]), 4))
+    for k in legs:
+        cell.update({f"{k}_ms_per_token": t[k], f"{k}_median": med(t[k]),
+                     f"{k}_host_ms_per_token_median": med([r["host_ms_per_token_median"] for r in legs[k]])})
+    return cell
+
+
 def time_lookup(eng, B, new, text_tokens, use_graph, kv, n, leg, ref):
     """One leg of --lookup: `new` tokens per sequence after the prefill.  leg "plain": the one-token step (returns the tokens [B, new + n] it
     chose, the other legs' drafts); "wrong" / "true": verify steps of n drafts that are all wrong / all right."""
@@ -319,8 +426,14 @@ def main():
                     help="N > 0: prompt-lookup decoding with N drafts per step: plain, always-wrong and always-right legs, --repeats runs each")
     ap.add_argument("--wide", action="store_true",
                     help="wide (one call) and chunked (16-row slices) GEMM legs alternately at B = 16, 32, 64 (--batches), --repeats runs each")
+    ap.add_argument("--select", action="store_true",
+                    help="torch, device and device_k50 token-selection legs alternately at B = 1, 8, 64 (--batches), eager and captured")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.select:
+        a.out = a.out or os.path.join(ROOT, "profiles", f"decode_bench_{a.model}_select.json")
+        if a.batches == "1,8":
+            a.batches = "1,8,64"
     if a.wide:
         a.out = a.out or os.path.join(ROOT, "profiles", f"decode_bench_{a.model}_wide.json")
         if a.batches == "1,8":
@@ -332,6 +445,24 @@ def main():
     dec_b, head_b = weight_bytes(eng)
     res = dict(model=a.model, layers=eng.cfg.num_hidden_layers, decoder_weight_gb=round(dec_b / 1e9, 3), lm_head_gb=round(head_b / 1e9, 3),
                roofline_ms_per_token_8tbps=round((dec_b + head_b) / 8e12 * 1e3, 3), runs=[])
+    def write():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(json.dumps(res) + "\n")
+
+    if a.select:
+        res.update(select=True, weights="bf16", kv="bf16", cells=[])
+
+        def on_run(r):
+            res["runs"].append(r)
+            write()
+
+        for B in [int(x) for x in a.batches.split(",")]:
+            for g in ((True,) if a.graph else (False, True)):
+                res["cells"].append(select_legs(eng, B, a.new, a.text, a.repeats, g, on_run))
+                write()
+        a.weights = a.kv = "select"                               # the other modes below do not run
     if a.wide:
         if a.weights != "bf16":
             eng.quantize_decoder(lm_head=True, fmt="e4m3" if a.weights == "fp8" else "mxfp4")
@@ -422,12 +553,8 @@ def main():
             r["weight_bytes_share_of_8tbps"] = round((dec_b + head_b) / 8e12 * 1e3 / r["ms_per_token"], 3)
             res["runs"].append(r)
             print(json.dumps(r), flush=True)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    print(json.dumps(res))
+    write()
 
 
 if __name__ == "__main__":

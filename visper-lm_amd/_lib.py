@@ -98,6 +98,8 @@ _SIGS = {
     "vp_decode_rope_append_kv8_rows": [i, i, i, i, p, l, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, l, p, p, p, p, i, p],
     "vp_decode_attn_kv8_rows": [i, i, i, i, i, p, l, p, l, l, p, l, l, p, l, l, p, l, l, p, l, p, p, i, f, i, p, p],
     "vp_decode_accept": [i, i, p, p, p, p, p, p, p],
+    # device-side token selection (HF's penalty -> temperature -> top-k -> top-p chain, greedy / inverse-CDF sampling, eos / pad bookkeeping)
+    "vp_decode_select": [i, i, p, l, i, f, i, f, f, p, p, i, p, i, i, p, p, p, p, l, i, p, l, p],
     "vp_ce_fwd_bwd": [l, i, p, l, p, p, f, i, p],
     "vp_emb_loss_workspace": [i, i, l],
     "vp_sumsq_nblk": [l],

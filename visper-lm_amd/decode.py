@@ -27,7 +27,14 @@ PromptLookupCandidateGenerator, greedy only) raises the tokens per step without 
             the same GEMM column, the same attention splits (nsplit of B sequences, not of the rows), the same argmax
   accept    vp_decode_accept keeps the leading drafts that equal the model's own choices and sets the next step's counters; the rows of
             rejected drafts are overwritten by the next step before anything reads them
-Tokens and logits are those of plain greedy decoding, bit for bit; only the number of steps changes."""
+Tokens and logits are those of plain greedy decoding, bit for bit; only the number of steps changes.
+
+Token selection.  Without top_k / repetition_penalty / device_sampling a token is chosen by plain torch between two steps (warp_logits /
+next_tokens: temperature, top-p, torch.multinomial) and the loop reads the host every token.  With one of them the step itself ends in
+vp_decode_select (ops.decode_select: HF's repetition penalty -> temperature -> top-k -> top-p on the raw logits, greedy or inverse-CDF
+sampling from uniforms drawn once per call, EOS / pad bookkeeping) and a counter increment, so the whole token is device work that a captured
+step replays; the host reads the finished flags every `sync_every` steps.  The penalised set is what THIS call emitted for the row: the
+reference reaches HF through `inputs_embeds`, so HF's processor sees the new tokens only."""
 from __future__ import annotations
 
 import os
@@ -153,6 +160,24 @@ def lookup_draft(history, n, max_ngram=2):
     return []
 
 
+def check_select(top_k=None, repetition_penalty=None, device_sampling=None, sync_every=1, lookup=0):
+    """The token-selection arguments of generate() -> (top_k, repetition_penalty, sync_every, device): top_k 0 / repetition_penalty 1.0 =
+    off; device = the selector runs on the device (vp_decode_select) — iff top_k > 0, repetition_penalty != 1 or device_sampling is true.
+    Host-only, before any GPU work, after check_lookup / check_batch."""
+    top_k = 0 if top_k is None else int(top_k)
+    if top_k < 0:
+        raise ValueError(f"top_k = {top_k}: must be >= 0 (0 / None = off)")
+    theta = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if not theta > 0 or theta == float("inf"):
+        raise ValueError(f"repetition_penalty = {repetition_penalty}: must be > 0 and finite (1.0 / None = off)")
+    if int(sync_every) < 1:
+        raise ValueError(f"sync_every = {sync_every}: must be >= 1 (the host reads the finished flags every sync_every steps)")
+    if lookup and (theta != 1.0 or device_sampling):
+        raise ValueError("prompt_lookup_num_tokens with repetition_penalty / device_sampling: the verify step accepts a draft iff it is the "
+                         "plain argmax of its row; a penalised or device-selected verify step is not built")
+    return top_k, theta, int(sync_every), bool(top_k > 0 or theta != 1.0 or device_sampling)
+
+
 def text_plan(eng, input_ids, attention_mask):
     """No-splice prefill input (text-only generate of the PT classes: base_ola_vlm.py:606-607 embeds the tokens as they are): each
     sequence's valid tokens left-aligned in [B*S, H] rows gathered from the embedding table.  Returns (x, plan) with the plan fields
@@ -191,6 +216,7 @@ class DecodeSession:
     prefill(); sessions of at most 16 rows do not read it."""
 
     wide_gemm = None
+    sel = None                                                   # device-side token selection (alloc_select): the step then ends in it
 
     def __init__(self, eng, kv_cache_dtype=None, lookup=None):
         self.eng = eng
@@ -335,6 +361,43 @@ class DecodeSession:
             ops.decode_accept(self.next32, self.tok, self.base_pos, self.vpos, self.vkv, self.n_acc, self.lookup)
         else:
             ops.add_i32_(c.lens, 1)
+        if self.sel is not None:                                 # the whole token is device work: the choice lands in `tok`, where the next
+            self._select(self.logits)                            # step's gather reads it
+
+    # ---------------------------------------------------------------------------------------------- device-side selection
+    def alloc_select(self, B, N, eos, pad, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, generator=None):
+        """Turn the session's step into step + vp_decode_select: the buffers one call owns.  finished / col / out [B, N] int32, the `seen`
+        bitmap (penalty only) and, for sampling, `uniforms` [N, B]: drawn once, on the generator's device, so a seeded call reproduces."""
+        assert not self.lookup and self.graph is None
+        dev = self.eng.dev
+        V = self.eng.fz["lm_head"].shape[0]
+        self.finished = torch.zeros(B, device=dev, dtype=I32)
+        self.col = torch.zeros(1, device=dev, dtype=I32)
+        self.out = torch.zeros(B, max(int(N), 1), device=dev, dtype=I32)
+        self.seen = torch.zeros(B, (V + 31) // 32, device=dev, dtype=I32) if repetition_penalty != 1.0 else None
+        self.eos_t = torch.tensor(eos, device=dev, dtype=I32) if eos else None
+        self.uniforms = None
+        if do_sample:
+            gdev = generator.device if generator is not None else dev
+            self.uniforms = torch.rand(max(int(N), 1), B, generator=generator, device=gdev, dtype=torch.float32).to(dev)
+        self.sel = dict(do_sample=bool(do_sample), temperature=float(temperature) if do_sample else 1.0, top_k=int(top_k) if do_sample else 0,
+                        top_p=float(top_p) if do_sample else 1.0, repetition_penalty=float(repetition_penalty), pad=int(pad))
+
+    def _select(self, logits):
+        """Select column `col` from `logits` [B, V] into tok / out / finished, then col += 1 (two launches; inside the step they are
+        captured with it)."""
+        ops.decode_select(logits, self.tok, self.out, self.col, self.finished, seen=self.seen, u=self.uniforms, eos=self.eos_t, **self.sel)
+        ops.add_i32_(self.col, 1)
+
+    def select_first(self, logits):
+        """The first token, from the prefill's logits: the same entry point, outside the captured step."""
+        self._select(logits)
+
+    def step_select(self):
+        """One step on the token the selector left in `tok`, ending in the next selection -> the step's RAW logits (a view)."""
+        self._launch()
+        self.cache.lens_host += 1
+        return self.logits
 
     def _attend_rows(self, l, window):
         """RoPE + append + attention of layer l in verify mode: the plain step's three cache formats through the *_rows entry points."""
@@ -422,16 +485,27 @@ def next_tokens(logits, do_sample=False, temperature=1.0, top_p=1.0, generator=N
 
 def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None, max_new_tokens=20, do_sample=False, temperature=1.0,
              top_p=1.0, eos_token_id=None, pad_token_id=None, streamer=None, generator=None, use_graph=None, return_logits=False,
-             kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, drafter=None):
+             kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, drafter=None, top_k=None,
+             repetition_penalty=None, device_sampling=None, sync_every=1):
     """Greedy / sampled decoding of B prompts, each continuing at its own length -> LongTensor [B, n_new] of the new tokens only (rows that
     finished are padded with pad_token_id after their EOS); B <= 64 (check_batch).  return_logits: also the fp32 logits [B, V] each token was chosen from.
     kv_cache_dtype: None (the engine's default, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated" (KVCache).
     prompt_lookup_num_tokens = n > 0 (HF's argument; greedy only, B (n + 1) <= 16): prompt-lookup decoding with n drafts per step from
     lookup_draft(history, n, max_matching_ngram_size), or from drafter(b, history) -> list of ids (no HF argument: the test and benchmark
-    hook).  The result, the streamer calls and the logits are those of the plain path."""
+    hook).  The result, the streamer calls and the logits are those of the plain path.
+    top_k (HF; sampling only, like HF's warper) / repetition_penalty (HF; over the tokens this call emitted) / device_sampling=True: tokens
+    are selected on the device (vp_decode_select; module docstring).  Greedy tokens are those of the torch path; sampled tokens follow the
+    same distribution from their own random stream (`sess.uniforms`, torch.rand(max_new_tokens, B, generator=generator)), not
+    torch.multinomial's.  sync_every: the host reads the finished flags every that many steps (a streamer forces 1); the result does not
+    depend on it, only the number of steps run past the last EOS.  Without these arguments every launch and every token is the torch path's."""
     B = input_ids.shape[0]
     lookup = check_lookup(B, prompt_lookup_num_tokens, do_sample, max_matching_ngram_size)
     check_batch(B)
+    top_k, repetition_penalty, sync_every, device = check_select(top_k, repetition_penalty, device_sampling, sync_every, lookup)
+    if device and not lookup:
+        return _generate_device(eng, input_ids, attention_mask, images, group_sizes, int(max_new_tokens), do_sample, temperature, top_p,
+                                top_k, repetition_penalty, eos_token_id, pad_token_id, streamer, generator, use_graph, return_logits,
+                                kv_cache_dtype, sync_every)
     if lookup:
         return _generate_lookup(eng, input_ids, attention_mask, images, group_sizes, int(max_new_tokens), eos_token_id, pad_token_id, streamer,
                                 use_graph, return_logits, kv_cache_dtype, lookup, int(max_matching_ngram_size), drafter)
@@ -468,6 +542,56 @@ def generate(eng, input_ids, attention_mask=None, images=None, group_sizes=None,
     if streamer is not None:
         streamer.end()
     res = torch.stack(out, 1) if out else torch.empty(B, 0, dtype=torch.long, device=eng.dev)
+    sess.graph = None
+    if return_logits:
+        return res, kept, sess
+    return res
+
+
+def _generate_device(eng, input_ids, attention_mask, images, group_sizes, N, do_sample, temperature, top_p, top_k, repetition_penalty,
+                     eos_token_id, pad_token_id, streamer, generator, use_graph, return_logits, kv_cache_dtype, sync_every):
+    """generate() with the selector on the device.  Column i of `sess.out` is written by the step that computed its logits; the host only
+    reads `finished` (and, for a streamer, the new column) every sync_every steps.  Rows that finished emit pad, so whatever ran past the
+    column at which the plain loop would have stopped is cut off at the end: the result is the plain loop's for every sync_every."""
+    B = input_ids.shape[0]
+    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(t) for t in eos_token_id])
+    if pad_token_id is None:
+        pad_token_id = eos[0] if eos else 0
+    temperature = 1.0 if temperature is None else float(temperature)
+    top_p = 1.0 if top_p is None else float(top_p)
+    if do_sample and not (temperature > 0 and 0 < top_p <= 1):
+        raise ValueError(f"temperature = {temperature} must be > 0 and top_p = {top_p} in (0, 1]")
+    sess = DecodeSession(eng, kv_cache_dtype)
+    if use_graph is not None:
+        sess.use_graph = bool(use_graph)
+    if streamer is not None:
+        streamer.put(input_ids.cpu())
+        sync_every = 1
+    kept, n = [], 0
+    with torch.no_grad():
+        if N > 0:
+            logits = sess.prefill(input_ids, attention_mask, images, group_sizes, N)
+            sess.alloc_select(B, N, eos, pad_token_id, do_sample, temperature, top_k, top_p, repetition_penalty, generator)
+        for i in range(N):
+            if i == 0:
+                sess.select_first(logits)
+            else:
+                logits = sess.step_select()
+            if return_logits:
+                kept.append(logits.clone())
+            n = i + 1
+            if streamer is not None:
+                streamer.put(sess.out[:, i].to(torch.long).cpu())
+            if eos and (n % sync_every == 0 or n == N) and bool((sess.finished != 0).all()):
+                break
+        res = sess.out[:, :n].to(torch.long) if n else torch.empty(B, 0, dtype=torch.long, device=eng.dev)
+        if eos and n:                                            # the column after which the plain loop stops: the first at which every row is finished
+            done = (torch.isin(res, torch.tensor(eos, device=res.device)).cumsum(1) > 0).all(0)
+            if bool(done.any()):
+                n = int(torch.nonzero(done)[0]) + 1
+                res, kept = res[:, :n].contiguous(), kept[:n]
+    if streamer is not None:
+        streamer.end()
     sess.graph = None
     if return_logits:
         return res, kept, sess

@@ -152,6 +152,10 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
     max_ngram = 2 if max_ngram is None else int(max_ngram)
     lookup = decode.check_lookup(inputs.shape[0], lookup, do_sample, max_ngram)
     decode.check_batch(inputs.shape[0])                              # more sequences than a decode step takes: refused before the engine is built
+    # token selection (HF's top_k / repetition_penalty; device_sampling / sync_every are not HF arguments): decode.check_select
+    top_k, repetition_penalty = kwargs.pop("top_k", None), kwargs.pop("repetition_penalty", None)
+    device_sampling, sync_every = kwargs.pop("device_sampling", None), kwargs.pop("sync_every", 1)
+    decode.check_select(top_k, repetition_penalty, device_sampling, sync_every, lookup)
     with torch.no_grad():
         module._sync_trainable()
         eng = module._get_engine()
@@ -166,7 +170,8 @@ def _generate(module, inputs=None, images=None, image_sizes=None, attention_mask
         return decode.generate(eng, inputs, attention_mask, images, gsz, max_new_tokens=max_new_tokens, do_sample=do_sample,
                                temperature=temperature, top_p=top_p, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                streamer=streamer, generator=generator, kv_cache_dtype=kv_cache_dtype,
-                               prompt_lookup_num_tokens=lookup, max_matching_ngram_size=max_ngram)
+                               prompt_lookup_num_tokens=lookup, max_matching_ngram_size=max_ngram, top_k=top_k,
+                               repetition_penalty=repetition_penalty, device_sampling=device_sampling, sync_every=sync_every)
 
 
 class _VisperStep(torch.autograd.Function):
@@ -604,7 +609,9 @@ class _OlaCausalLMBase(OlaLlavaMetaForCausalLM, BaseOLA_VLM, EngineModule):
         """base_ola_vlm.py:579-616: with `images` the prompt is spliced (image features + task tokens, ola_arch.py:256-444); with
         images=None it is the token embeddings alone (base_ola_vlm.py:606-607).  -> LongTensor [B, n_new] (new tokens only).
         kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated".
-        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps)."""
+        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps).
+        top_k / repetition_penalty (HF; the penalty covers the tokens this call emitted), device_sampling=True, sync_every=n (in **kwargs):
+        token selection on the device (vp_decode_select), the host reading the finished flags every n steps; decode.generate's docstring."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
                          pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype,
                          prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, **kwargs)

@@ -156,7 +156,9 @@ class _LlavaCausalLMBase(LlavaMetaForCausalLM, EngineModule):
         """llava_llama.py:122-153: images -> prepare_inputs_labels_for_multimodal's splice, else the token embeddings alone; then HF
         generation over inputs_embeds.  -> LongTensor [B, n_new] (new tokens only).
         kv_cache_dtype: None (the default quantize_kv_cache_for_generation() set, initially bf16) | "bf16" | "fp8_e4m3" | "fp8_e4m3_emulated".
-        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps)."""
+        prompt_lookup_num_tokens / max_matching_ngram_size: HF's prompt-lookup decoding (greedy; the same tokens in fewer steps).
+        top_k / repetition_penalty (HF; the penalty covers the tokens this call emitted), device_sampling=True, sync_every=n (in **kwargs):
+        token selection on the device (vp_decode_select), the host reading the finished flags every n steps; decode.generate's docstring."""
         return _generate(self, inputs, images, image_sizes, attention_mask, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
                          pad_token_id, num_beams, use_cache, streamer, generator, kv_cache_dtype=kv_cache_dtype,
                          prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size, **kwargs)

@@ -926,6 +926,35 @@ def decode_accept(next_tok, tok, base_pos, pos, kv_len, n_acc, n):
     return n_acc
 
 
+def decode_select(logits, tok, out, col, finished, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seen=None,
+                  u=None, eos=None, pad=0, scores_out=None):
+    """Select one token per row of RAW fp32 logits [R, V] on the device (vp_decode_select: HF's repetition penalty -> temperature -> top-k ->
+    top-p, then greedy or inverse-CDF sampling).  int32 on the device: tok [R] <- the raw choice, out [R, n_out] column col[0] <- pad for a
+    row that was finished, else the choice, finished [R] |= (that output is in eos [n_eos]); col: one int32.  seen: int32 / uint32
+    [R, ceil(V / 32)] bitmap of the tokens the row was given before (required when repetition_penalty != 1; the chosen token's bit is set).
+    u: fp32 [R] or [steps, R] uniforms in [0, 1) (row min(col, steps - 1) is read; required when do_sample).  scores_out: fp32 [R, V] <- the
+    processed scores (-inf where removed).  The logits are not modified.  Sampling follows torch.multinomial's distribution on its own random
+    stream (the uniforms), not torch's."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1, (logits.shape, logits.dtype, logits.stride())
+    R, V = logits.shape
+    for t, m in ((tok, R), (finished, R), (col, 1)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == m, (t.shape, t.dtype, m)
+    assert out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] == R and out.stride(1) == 1, (out.shape, out.dtype, out.stride())
+    if seen is not None:
+        assert seen.dtype in (torch.int32, torch.uint32) and seen.is_contiguous() and tuple(seen.shape) == (R, (V + 31) // 32), seen.shape
+    if u is not None:
+        assert u.dtype == torch.float32 and u.is_contiguous() and u.shape[-1] == R and u.dim() in (1, 2), (u.shape, u.dtype)
+    if eos is not None:
+        assert eos.dtype == torch.int32 and eos.is_contiguous() and eos.dim() == 1, (eos.shape, eos.dtype)
+    if scores_out is not None:
+        assert scores_out.dtype == torch.float32 and tuple(scores_out.shape) == (R, V) and scores_out.stride(1) == 1, scores_out.shape
+    _lib.call("vp_decode_select", R, V, _p(logits), logits.stride(0), int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
+              float(repetition_penalty), _p(seen), _p(u), 1 if u is None or u.dim() == 1 else u.shape[0], _p(eos),
+              0 if eos is None else eos.numel(), int(pad), _p(finished), _p(col), _p(tok), _p(out), out.stride(0), out.shape[1],
+              _p(scores_out), 0 if scores_out is None else scores_out.stride(0), _stream())
+    return tok
+
+
 def add_i32_(x, delta=1):
     assert x.dtype == torch.int32 and x.is_contiguous()
     _lib.call("vp_add_i32", x.numel(), _p(x), int(delta), _stream())
